@@ -15,6 +15,14 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W           (single GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps and prints
+one JSON result line (ms_per_step = wall time of one timed step).
+  --dump-outputs DIR : also write what the last timed step computed
+                       (loss, logits, updated parameters) as float32
+                       DIR/<name>.npy; same arguments, same inputs
+  --full             : anything measured beyond the headline figure
+                       runs only under this flag
 """
 
 import argparse
@@ -65,6 +73,15 @@ def parse_args():
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--comm-dtype", type=str, default="fp32", choices=["fp32", "bf16"])
     p.add_argument("--json-out", type=str, default=None)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, logits, updated parameters) "
+                        "as DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure; a plain run times the steps and nothing "
+                        "else (there are no extra measurements yet: this "
+                        "is where they go)")
     p.add_argument("--backend", type=str, default="auto",
                    choices=["auto", "nccl", "gloo"])
     p.add_argument("--sync-mode", type=str, default="dist_sync",
@@ -79,6 +96,31 @@ def parse_args():
                    help="disable NHWC layout (NHWC avoids MIOpen's "
                         "batched_transpose + slow NCHW pooling kernels)")
     return p.parse_args()
+
+
+# --dump-outputs budget: arrays above the per-array cap are written as a
+# fixed, seeded sample of their elements; everything together stays
+# under 48 MB of float32
+DUMP_ARRAY_ELEMS = 1 << 20
+DUMP_TOTAL_ELEMS = 12 << 20
+
+
+def dump_outputs(path, tensors):
+    """Write each tensor as path/<name>.npy (float32). With the same
+    arguments the sample indices are the same from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(1234)
+    left = DUMP_TOTAL_ELEMS
+    for name, t in tensors.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        cap = min(DUMP_ARRAY_ELEMS, left)
+        if a.size > cap:
+            idx = np.sort(rng.integers(0, a.size, size=cap))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -137,11 +179,14 @@ def main():
     amp_dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     amp = args.dtype == "bf16"
 
+    last = {}  # what the most recent step returned (no sync: refs only)
+
     def one_step():
         with torch.autocast(device_type=device_str, dtype=amp_dtype,
                             enabled=amp):
             out = model(x)
             loss = torch.nn.functional.cross_entropy(out, y)
+        last["logits"], last["loss"] = out, loss
         trainer.zero_grad()
         loss.backward()
         trainer.step()
@@ -186,6 +231,12 @@ def main():
         t = torch.tensor([elapsed], device=device if backend == "nccl" else "cpu")
         distmod.all_reduce(t, op=distmod.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        tensors = dict(last)
+        for name, prm in model.named_parameters():
+            tensors["param." + name] = prm
+        dump_outputs(args.dump_outputs, tensors)
 
     samples = world * bs * args.steps
     sps = samples / elapsed

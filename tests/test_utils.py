@@ -169,11 +169,14 @@ def test_profiler_wrapper(tmp_path):
     assert os.path.exists(out)
 
 
-def test_server_profiler_command_single():
+def test_server_profiler_command_single(tmp_path, monkeypatch):
     from geomx_amd import Config
     from geomx_amd.kvstore import create
     from geomx_amd.utils import profiler as prof
 
+    # the default profiler dumps rank<N>_profile.json relative to the
+    # working directory: keep it out of the source tree
+    monkeypatch.chdir(tmp_path)
     kv = create("dist_sync", cfg=Config.from_env(device="cpu"))
     prof.send_server_profiler_command(kv, prof.ServerProfilerCommand.STATE,
                                       "run")
