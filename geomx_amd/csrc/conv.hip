@@ -20,8 +20,9 @@
 //
 // Each wave owns whole (n, ho) output rows (row-walk: no per-tile
 // 64-bit div/mod) and slides across the row's tiles with incremental
-// addresses. Border tiles of the padded data-grad pass take a masked
-// scalar-gather path; interior tiles take the vector path.
+// addresses. The direct kernel is interior-only: the data-grad pass
+// either zero-pads its input physically or runs the LDS-staged kernel,
+// which materialises the border while staging.
 //
 // Requirements: CI % 4 == 0 (conv1's 3 channels are zero-padded to 4
 // by the Python wrapper), CO % 16 == 0, kernel 5x5, stride 1.
@@ -43,7 +44,7 @@ __device__ __forceinline__ bf16_t cf2bf(float f) {
   return (bf16_t)((cv.u + 0x7FFFu + lsb) >> 16);
 }
 
-template <int CI, int COT, int PAD>
+template <int CI, int COT>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
     const bf16_t* __restrict__ in,       // [N][Hi][Wi][CI]
     const bf16_t* __restrict__ w_frags,  // [COT][nK][64][8]
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
     const long long in_n = (long long)n * Hi * Wi * CI;
     const long long out_row = ((long long)n * Ho + ho) * (long long)Wo * CO;
 
-    // chunked fragment loader (PAD==0 kernels: loads are always
+    // chunked fragment loader (interior-only kernel: loads are always
     // in-bounds once the lane's pixel is clamped to Wo-1, because
     // (Wo-1) + 5 taps == Wi exactly). CH frags per chunk keeps the
     // double-buffer register cost at 2*CH*4 VGPRs regardless of nK.
@@ -111,8 +112,8 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
     auto load_chunk = [&](int tw, int c, bf16x8(&dst)[CH]) {
       const int wo_raw = (tw << 4) + p;
       const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      const long long e_base = in_n + (long long)(wo - PAD) * CI +
-                               (long long)(ho - PAD) * (Wi * CI);
+      const long long e_base = in_n + (long long)wo * CI +
+                               (long long)ho * (Wi * CI);
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const int km = c * CH + j;
@@ -826,49 +827,36 @@ int geops_conv5_nhwc(const bf16_t* in, const bf16_t* w_frags,
                      hipStream_t s) {
   const long long rows = (long long)Nn * Ho;
   const dim3 grid(conv_blocks(rows)), block(CONV_THREADS);
-#define LAUNCH(CI_, COT_, PAD_)                                          \
-  hipLaunchKernelGGL((k_conv5_nhwc<CI_, COT_, PAD_>), grid, block, 0, s, \
-                     in, w_frags, bias, out, Nn, Hi, Wi, Ho, Wo);        \
-  return 0;
-  // pad handling is done by the caller (physical zero-padding of the
-  // data-grad input); every variant is the interior-only PAD=0 kernel
-  if ((pad == 0 || pad == 4) && CI == 32 && CO == 16) {
+  // pad == 0: `in` carries every pixel the taps touch (the data-grad
+  // caller zero-pads grad_out physically). pad == 4: `in` is the
+  // UNPADDED tensor, Hi/Wi still count the virtual 4-pixel border, and
+  // the LDS kernel materialises it while staging -- CI=32, CO=16 only
+  // (the conv2 data gradient). The LDS variants are compiled for 120-
+  // and 232-pixel staging rows; wider pad-0 rows fall through to the
+  // direct kernel, which has no width limit.
+  if (CI == 32 && CO == 16) {
     const int W16 = (Wo + 15) >> 4;
     const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
     long long prows = (long long)Nn * ((Ho + 1) / 2);
     int n_wg = (int)((prows < 4096) ? prows : 4096);
-    if (pad == 4 && need <= 120) {
-      hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, 120, 4>), dim3(n_wg),
-                         dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,
-                         Nn, Hi, Wi, Ho, Wo);
-      return 0;
-    }
-    if (pad == 4 && need <= 232) {
-      hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, 232, 4>), dim3(n_wg),
-                         dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,
-                         Nn, Hi, Wi, Ho, Wo);
-      return 0;
-    }
-    if (need <= 120) {
-      hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, 120>), dim3(n_wg),
-                         dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,
-                         Nn, Hi, Wi, Ho, Wo);
-      return 0;
-    }
-    if (need <= 232) {
-      hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, 232>), dim3(n_wg),
-                         dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,
-                         Nn, Hi, Wi, Ho, Wo);
-      return 0;
-    }
+#define LDSLAUNCH(PIX_, PAD_)                                             \
+  if (pad == PAD_ && need <= PIX_) {                                      \
+    hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, PAD_>), dim3(n_wg), \
+                       dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,  \
+                       Nn, Hi, Wi, Ho, Wo);                               \
+    return 0;                                                             \
   }
-  if (pad == 0) {
-    if (CI == 4 && CO == 16) { LAUNCH(4, 1, 0) }
-    if (CI == 16 && CO == 32) { LAUNCH(16, 2, 0) }
-    if (CI == 16 && CO == 16) { LAUNCH(16, 1, 0) }
-    if (CI == 32 && CO == 16) { LAUNCH(32, 1, 0) }
-    if (CI == 32 && CO == 32) { LAUNCH(32, 2, 0) }
+    LDSLAUNCH(120, 4) LDSLAUNCH(232, 4) LDSLAUNCH(120, 0) LDSLAUNCH(232, 0)
+#undef LDSLAUNCH
   }
+  if (pad != 0) return -1;
+#define LAUNCH(CI_, COT_)                                                 \
+  if (CI == CI_ && CO == COT_ * 16) {                                     \
+    hipLaunchKernelGGL((k_conv5_nhwc<CI_, COT_>), grid, block, 0, s, in,  \
+                       w_frags, bias, out, Nn, Hi, Wi, Ho, Wo);           \
+    return 0;                                                             \
+  }
+  LAUNCH(4, 1) LAUNCH(16, 2) LAUNCH(16, 1) LAUNCH(32, 1) LAUNCH(32, 2)
 #undef LAUNCH
   return -1;
 }

@@ -2,10 +2,10 @@
 //
 // dW[kh,kw,ci][o] = sum_{n,ho,wo} in[n,ho+kh,wo+kw,ci] * gout[n,ho,wo,o]
 //
-// v1 (convwrw.hip) stages TRANSPOSED images with per-element ds writes
-// and gathers the shifted A fragment with an alignbyte funnel; it is
-// LDS-gather bound (1.10 ms standalone on the conv2 shape vs MIOpen's
-// 1.60 in-step). v2 removes both costs:
+// v1 (removed; see git history) staged TRANSPOSED images with
+// per-element ds writes and gathered the shifted A fragment with an
+// alignbyte funnel; it was LDS-gather bound (1.10 ms standalone on the
+// conv2 shape vs MIOpen's 1.60 in-step). v2 removes both costs:
 //
 //   * LDS images keep the NATURAL pixel-major layout ([pix][ci] for the
 //     input — identical to global NHWC — and per-o-tile [pix][16] for
@@ -26,7 +26,7 @@
 // rows; 4 waves split the 25 (kh,kw) tap tiles round-robin and each
 // wave computes BOTH o-tiles for its taps (A-fragment reuse), keeping
 // all accumulators in VGPRs until one final per-workgroup slab flush
-// (partials summed in torch, same contract as v1).
+// (partials summed in torch).
 
 #include <hip/hip_runtime.h>
 
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
     float* __restrict__ part,         // [nWG][176][16]
     int Nn, int Hi, int Wi, int Ho, int Wo) {
   // v3: the transpose read gathers PER-LANE 8B quarters (verified by
-  // scripts/tr16_scatter_probe.py: out[m][j] = mem[addr[4j+(m>>2)] +
+  // test_tr16_per_lane_gather: out[m][j] = mem[addr[4j+(m>>2)] +
   // (m&3) elems]), so the A fragment (lane m = kho*4+ci) reads STRAIGHT
   // from the 6 raw [pix][4] input rows: lane l points at
   // row(r + khg*4 + (l&3)), pixel (pix0 + kw + 4q + (l>>2)&3).
@@ -469,72 +469,6 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
   }
 }
 
-// debug: run block 0's staging for (n=0, ho0=0) and dump the raw LDS
-// bytes so tests can check the glds images independently of the MFMAs.
-template <int COT, int PIX>
-__global__ void k_wrw2_dump(const bf16_t* __restrict__ in,
-                            const bf16_t* __restrict__ gout,
-                            bf16_t* __restrict__ dump,
-                            int Nn, int Hi, int Wi, int Ho, int Wo) {
-  constexpr int CI = 16;
-  constexpr int CO = COT * 16;
-  constexpr int ROW_BYTES = PIX * CI * 2;
-  constexpr int NCH = (ROW_BYTES + 1023) / 1024;
-  constexpr int RPB = NCH * 1024;
-  constexpr int NROW_IN = WRW2_R + 4;
-  constexpr int NROW_GO = WRW2_R * COT;
-  __shared__ __attribute__((aligned(128))) char lds_all[(NROW_IN + NROW_GO) *
-                                                        RPB];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int nrows = Ho < WRW2_R ? Ho : WRW2_R;
-  const int irows = nrows + 4;
-  {
-    const int nchunks_a = irows * NCH;
-    for (int t = wid; t < nchunks_a; t += 4) {
-      const int ir = t / NCH;
-      const int c = t - ir * NCH;
-      const int slot = c * 64 + lane;
-      const int pix = slot >> 1;
-      const bf16_t* src = (pix < Wi)
-          ? in + ((long long)ir * Wi * CI + (long long)slot * 8)
-          : g_wrw2_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all + ir * RPB +
-                                                    c * 1024),
-          16, 0, 0);
-    }
-    const int nchunks_b = nrows * COT * NCH;
-    for (int t = wid; t < nchunks_b; t += 4) {
-      const int rr = t / (COT * NCH);
-      const int rem = t - rr * (COT * NCH);
-      const int ot = rem / NCH;
-      const int c = rem - ot * NCH;
-      const int slot = c * 64 + lane;
-      const int pix = slot >> 1;
-      const int half = slot & 1;
-      const bf16_t* src = (pix < Wo)
-          ? gout + ((long long)rr * Wo * CO + (long long)pix * CO +
-                    ot * 16 + half * 8)
-          : g_wrw2_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all +
-                                                    (NROW_IN + rr * COT +
-                                                     ot) * RPB + c * 1024),
-          16, 0, 0);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const bf16_t* l16 = (const bf16_t*)lds_all;
-  for (int i = threadIdx.x; i < (NROW_IN + NROW_GO) * RPB / 2;
-       i += blockDim.x)
-    dump[i] = l16[i];
-}
-
-
 // probe 2: SCATTERED per-lane addresses. If the transpose read gathers
 // each lane's own 8B quarter (out[g][j] = mem[addr[4j+(g>>2)] + 2*(g&3)])
 // the wrw4 staging can drop its interleaved-image duplication. in: 512
@@ -602,19 +536,6 @@ void geops_tr16_probe2(const bf16_t* in, const int* addr_off, bf16_t* out,
                        hipStream_t s) {
   hipLaunchKernelGGL(k_tr16_probe2, dim3(1), dim3(64), 0, s, in, addr_off,
                      out);
-}
-
-// dump size in bf16 elements for the (COT,PIX) variant, or -1
-int geops_wrw2_dump(const bf16_t* in, const bf16_t* gout, bf16_t* dump,
-                    int Nn, int Hi, int Wi, int Ho, int Wo, int CO,
-                    hipStream_t s) {
-  if (CO == 32) {
-    constexpr int RPB = ((136 * 16 * 2 + 1023) / 1024) * 1024;
-    hipLaunchKernelGGL((k_wrw2_dump<2, 136>), dim3(1), dim3(WRW2_THREADS),
-                       0, s, in, gout, dump, Nn, Hi, Wi, Ho, Wo);
-    return (6 + 4) * RPB / 2;
-  }
-  return -1;
 }
 
 }  // extern "C"

@@ -1,4 +1,7 @@
-// Torch bindings for the geomx_amd gfx950 kernel library (kernels.hip).
+// Torch bindings for the geomx_amd gfx950 kernel library: kernels.hip
+// (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
+// (5x5 conv forward / data gradient) and convwrw2.hip (5x5 conv weight
+// gradient, tr16 probes).
 //
 // Thin checked wrappers: dtype/contiguity/device checks, stream plumbing
 // (kernels run on the current torch stream so they order correctly with
@@ -12,7 +15,7 @@
 
 #include <cstdint>
 
-// C-ABI launchers from kernels.hip
+// C-ABI launchers from the .hip files
 extern "C" {
 void geops_quantize_2bit(const float*, float*, uint32_t*, long long, float,
                          hipStream_t);
@@ -64,9 +67,6 @@ int geops_conv5_pool_nhwc(const unsigned short*, const unsigned short*,
                           int, int, int, int, int, hipStream_t);
 void geops_pad_ch3to4_nhwc(const void*, unsigned short*, long long, int,
                            hipStream_t);
-int geops_conv5_wrw_nhwc(const unsigned short*, const unsigned short*,
-                         float*, int, int, int, int, int, int, int, int,
-                         hipStream_t);
 int geops_conv5_wrw16_nhwc(const unsigned short*, const unsigned short*,
                            float*, int, int, int, int, int, int, int, int,
                            hipStream_t);
@@ -76,9 +76,6 @@ int geops_conv5_wrw4_nhwc(const unsigned short*, const unsigned short*,
 void geops_tr16_probe(const unsigned short*, unsigned short*, hipStream_t);
 void geops_tr16_probe2(const unsigned short*, const int*, unsigned short*,
                        hipStream_t);
-int geops_wrw2_dump(const unsigned short*, const unsigned short*,
-                    unsigned short*, int, int, int, int, int, int,
-                    hipStream_t);
 }
 
 namespace {
@@ -327,33 +324,18 @@ void conv5_wrw_nhwc(torch::Tensor in, torch::Tensor gout, torch::Tensor part,
   TORCH_CHECK(in.scalar_type() == torch::kBFloat16 &&
               gout.scalar_type() == torch::kBFloat16 &&
               part.scalar_type() == torch::kFloat32);
-  // CI=16 shapes go to the v2 kernel (LDS-DMA staging + tr16 reads);
-  // GEOPS_WRW_V1=1 forces the v1 path for A/B runs
-  static const bool force_v1 = [] {
-    const char* e = getenv("GEOPS_WRW_V1");
-    return e && e[0] == '1';
-  }();
-  int rc = -1;
-  if (CI == 4 && CO == 16 && !force_v1)
-    rc = geops_conv5_wrw4_nhwc(
-        (const unsigned short*)in.data_ptr(),
-        (const unsigned short*)gout.data_ptr(), part.data_ptr<float>(),
-        (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CI, (int)CO,
-        (int)n_wg, cur_stream());
-  if (CI == 16 && !force_v1)
-    rc = geops_conv5_wrw16_nhwc(
-        (const unsigned short*)in.data_ptr(),
-        (const unsigned short*)gout.data_ptr(), part.data_ptr<float>(),
-        (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CI, (int)CO,
-        (int)n_wg, cur_stream());
-  if (rc < 0)
-    rc = geops_conv5_wrw_nhwc(
-        (const unsigned short*)in.data_ptr(),
-        (const unsigned short*)gout.data_ptr(), part.data_ptr<float>(),
-        (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CI, (int)CO,
-        (int)n_wg, cur_stream());
+  // The two kernels write different slab layouts (ops/conv.py
+  // build_wrw_unpack_index), so there is no fallback between them: a
+  // geometry neither launcher accepts is an error.
+  const auto launch =
+      CI == 4 ? geops_conv5_wrw4_nhwc : geops_conv5_wrw16_nhwc;
+  const int rc = launch(
+      (const unsigned short*)in.data_ptr(),
+      (const unsigned short*)gout.data_ptr(), part.data_ptr<float>(),
+      (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CI, (int)CO,
+      (int)n_wg, cur_stream());
   TORCH_CHECK(rc > 0, "conv5_wrw_nhwc: unsupported geometry CI=", CI,
-              " CO=", CO, " Wo=", Wo);
+              " CO=", CO, " Wi=", Wi, " Wo=", Wo);
   launch_check("conv5_wrw_nhwc");
 }
 
@@ -468,17 +450,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
   m.def("conv5_wrw_nhwc", &conv5_wrw_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
-  m.def("wrw2_dump", [](torch::Tensor in, torch::Tensor gout,
-                        torch::Tensor dump, int64_t N, int64_t Hi,
-                        int64_t Wi, int64_t Ho, int64_t Wo, int64_t CO) {
-    const int sz = geops_wrw2_dump(
-        (const unsigned short*)in.data_ptr(),
-        (const unsigned short*)gout.data_ptr(),
-        (unsigned short*)dump.data_ptr(), (int)N, (int)Hi, (int)Wi,
-        (int)Ho, (int)Wo, (int)CO, cur_stream());
-    launch_check("wrw2_dump");
-    return (int64_t)sz;
-  });
   m.def("tr16_probe2", [](torch::Tensor in, torch::Tensor addr,
                           torch::Tensor out) {
     TORCH_CHECK(in.is_cuda() && addr.is_cuda() && out.is_cuda());

@@ -23,7 +23,6 @@ ext = CUDAExtension(
         "geomx_amd/csrc/geops.cpp",
         "geomx_amd/csrc/kernels.hip",
         "geomx_amd/csrc/conv.hip",
-        "geomx_amd/csrc/convwrw.hip",
         "geomx_amd/csrc/convwrw2.hip",
     ],
     extra_compile_args={

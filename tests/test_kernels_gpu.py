@@ -536,6 +536,28 @@ def test_tr16_lane_mapping():
         assert torch.equal(got[lane], expect), (lane, got[lane], expect)
 
 
+def test_tr16_per_lane_gather():
+    """ds_read_b64_tr_b16 with SCATTERED lane addresses: the read gathers
+    each lane's own 8-byte quarter, out[g][j] = mem[addr[4j+(g>>2)] +
+    (g&3)] within a 16-lane group. k_conv5_wrw4_nhwc builds its A
+    fragment on this (each lane points at a different raw input row)."""
+    from geomx_amd import _geops
+    content = torch.arange(512, dtype=torch.float32).to(torch.bfloat16)
+    # scattered 8B-aligned (multiple-of-4-element) offsets, one per lane
+    # of a group, replicated over the 4 groups
+    gen = torch.Generator().manual_seed(9)
+    addr = (torch.randperm(128, generator=gen)[:16] * 4).to(torch.int32)
+    out = torch.empty(256, dtype=torch.bfloat16, device=DEV)
+    _geops.tr16_probe2(content.to(DEV), addr.repeat(4).contiguous().to(DEV),
+                       out)
+    got = out.cpu().float().reshape(64, 4)
+    c = content.float()
+    for g in range(16):
+        for j in range(4):
+            expect = c[int(addr[4 * j + (g >> 2)]) + (g & 3)]
+            assert got[g, j] == expect, (g, j, got[g, j], expect)
+
+
 @pytest.mark.parametrize("ci,co,hw", [(16, 32, 70), (16, 16, 112),
                                       (16, 32, 110)])
 def test_conv5_wrw_v2_matches_aten(ci, co, hw):
@@ -708,3 +730,93 @@ def test_geo_cnn_gpu_full_model_grads():
         assert torch.allclose(a.grad.float(), b.grad.float(),
                               atol=0.05 * scale + 1e-5, rtol=0.05), \
             (a.grad.float() - b.grad.float()).abs().max()
+
+
+# ---------------------------------------------------------------------------
+# conv5 routing: module forward+backward at the widths where one of the
+# three ops changes kernel (or leaves the custom kernels for ATen)
+# ---------------------------------------------------------------------------
+
+ROUTING_CASES = [
+    # kind, ci, co, W, expected (fwd, dgrad, wrw)
+    ("direct", 3, 16, 35, ("direct", "direct_padded", "aten")),
+    ("pool", 3, 16, 228, ("pool", "direct_padded", "wrw4")),
+    ("pool", 3, 16, 230, ("pool", "direct_padded", "aten")),
+    ("pool", 16, 32, 116, ("pool", "lds_pad4", "wrw16")),
+    ("pool", 16, 32, 118, ("aten", "lds_pad4", "wrw16")),
+    ("pool", 16, 16, 20, ("pool", "direct_padded", "wrw16")),
+    ("direct", 16, 32, 224, ("direct", "lds_pad4", "wrw16")),
+    ("direct", 16, 32, 226, ("direct", "direct_padded", "wrw16")),
+    ("split", 16, 32, 230, ("aten", "direct_padded", "aten")),
+]
+
+
+@pytest.mark.parametrize("kind,ci,co,W,routes", ROUTING_CASES)
+def test_conv5_routing_boundaries_match_eager(kind, ci, co, W, routes):
+    """N=2, H=8 (Ho=4): y, x.grad, weight.grad and bias.grad of the
+    module vs eager. Pooled cases use the reference chain and the
+    tolerances of test_conv5_pool_fused_matches_eager; the others those
+    of test_conv5_fwd/backward_matches_aten ('direct') and
+    test_split_backward_conv2_grads_match ('split').
+
+    Pooled cases off the fused kernel (W=118) pool an fp32 ATen conv,
+    so the fp32 reference chain applies to them unchanged."""
+    from geomx_amd.ops.conv import GeoConv5, GeoConv5Pool, _SUPPORTED_FWD
+    fn = torch.nn.functional
+    torch.manual_seed(80)
+    if kind == "pool":
+        m = GeoConv5Pool(ci, co).to(DEV)
+    elif kind == "direct":
+        m = GeoConv5(ci, co, enabled_shapes=_SUPPORTED_FWD).to(DEV)
+    else:
+        m = GeoConv5(ci, co).to(DEV)
+    x = torch.randn(2, ci, 8, W, device=DEV, dtype=torch.bfloat16) \
+        .to(memory_format=torch.channels_last).requires_grad_(True)
+    assert tuple(m._route(x)[0]) == routes
+    y = m(x)
+    g = torch.randn_like(y)
+    y.backward(g)
+
+    def err(a, b):
+        return (a.float() - b.float()).abs().max().item()
+
+    if kind == "pool":
+        x2 = x.detach().float().requires_grad_(True)
+        w2 = m.weight.detach().to(torch.bfloat16).float().requires_grad_(True)
+        b2 = m.bias.detach().to(torch.bfloat16).float().requires_grad_(True)
+        y2 = fn.max_pool2d(fn.relu(fn.conv2d(x2, w2, b2)), 2, 2)
+        y2.backward(g.float())
+        gscale = x2.grad.abs().max().item()
+        wscale = m.weight.grad.abs().max().item() + 1e-6
+        print("routing", kind, ci, co, W, "err y/gx/gw/gb",
+              err(y, y2), err(x.grad, x2.grad), err(m.weight.grad, w2.grad),
+              err(m.bias.grad, b2.grad), "gscale", gscale, "wscale", wscale)
+        assert y.shape == y2.shape
+        assert torch.allclose(y.float(), y2, atol=0.1, rtol=0.05)
+        assert torch.allclose(x.grad.float(), x2.grad,
+                              atol=0.05 * gscale + 0.05, rtol=0.05)
+        assert torch.allclose(m.weight.grad, w2.grad,
+                              atol=0.03 * wscale + 0.5, rtol=0.05)
+        assert torch.allclose(m.bias.grad, b2.grad, atol=0.5, rtol=0.05)
+        return
+
+    x2 = x.detach().clone().requires_grad_(True)
+    w2 = m.weight.detach().clone().requires_grad_(True)
+    b2 = m.bias.detach().clone().requires_grad_(True)
+    y2 = fn.conv2d(x2, w2.to(torch.bfloat16), b2.to(torch.bfloat16))
+    y2.backward(g)
+    print("routing", kind, ci, co, W, "err y/gx/gw/gb", err(y, y2),
+          err(x.grad, x2.grad), err(m.weight.grad, w2.grad),
+          err(m.bias.grad, b2.grad))
+    assert y.shape == y2.shape
+    assert err(y, y2) < 0.05
+    if kind == "direct":
+        assert err(x.grad, x2.grad) < 0.1
+        w_atol = 0.5
+    else:
+        assert torch.allclose(x.grad.float(), x2.grad.float(), atol=0.1,
+                              rtol=0.05)
+        w_atol = 1.0
+    assert torch.allclose(m.weight.grad, w2.grad.float(), atol=w_atol,
+                          rtol=0.05)
+    assert torch.allclose(m.bias.grad, b2.grad.float(), atol=0.5, rtol=0.05)
