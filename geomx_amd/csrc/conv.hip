@@ -31,6 +31,8 @@
 
 #include <cstdint>
 
+#include "unpool.h"
+
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -626,16 +628,23 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool16_nhwc(
 // grad-out), CO=16 (the dgrad output channels). Same structure as the
 // fused pool16 kernel — block stages its 5 input rows + the weight
 // panel lives in LDS — but writes the full-resolution output (no pool).
-template <int CIT, int COT, int PIX, int PAD = 0>
+template <int CIT, int COT, int PIX, int PAD = 0, bool UNPOOL = false>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
     const bf16_t* __restrict__ in,   // [N][Hi-2P][Wi-2P][CI] (P virtual)
     const bf16_t* __restrict__ w_frags,  // [COT][nK][64][8]
     const float* __restrict__ bias,      // [CO] or nullptr
     bf16_t* __restrict__ out,            // [N][Ho][Wo][CO]
-    int Nn, int Hi, int Wi, int Ho, int Wo) {
+    int Nn, int Hi, int Wi, int Ho, int Wo,
+    const uint8_t* __restrict__ mask) {  // UNPOOL: argmax codes, as `in`
   // PAD>0: `in` is the UNPADDED tensor; the staging pass materialises
   // the zero border directly in LDS (granules map within one pixel for
   // CI>=8, so the border test is per-granule)
+  // UNPOOL (CI=32, PAD=4, Ho and Wo even): `in` is the max-POOLED
+  // tensor [N][(Hi-8)/2][(Wi-8)/2][CI] and `mask` its argmax codes; the
+  // staging pass expands each pooled pixel to its 4 full-resolution
+  // positions, so LDS holds what the PAD=4 staging of the scattered
+  // gradient would
+  static_assert(!UNPOOL || (CIT == 32 && PAD == 4), "conv2 dgrad only");
   constexpr int CI = CIT;
   constexpr int S = 5 * CI;
   constexpr int Sp = (S + 7) & ~7;
@@ -682,7 +691,62 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
     const long long n = blk / hblocks;
     const int ho0 = hb * ROWS;
     const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
-    for (int t = wid; t < (nrows + 4) * NCHA; t += 4) {
+    if constexpr (UNPOOL) {
+      // staged row ir is real row ho0 + ir - 4 and staged pixel pix is
+      // real pixel pix - 4, both even-aligned: the 6 rows are pooled
+      // rows (ho0>>1) - 2 + k, k = 0..2, and pixels (2pp, 2pp+1) are
+      // pooled pixel pp - 2. Item `it` = (k, pp, s): channel granule s
+      // (8 channels, 16 B + 8 mask bytes, contiguous in global memory
+      // along (pp, s)) of one pooled pixel, written to its 4 full-
+      // resolution positions under the same XOR swizzle as below
+      // (granule s sits at sub-slot s ^ ((pix>>2)&3), and pix>>2 ==
+      // pp>>1 for both pixels). Items outside the image write the zero
+      // border / tail. Loads first, then the selects and ds_writes.
+      constexpr int PPR = NCHA * 8;          // pooled pixels per LDS row
+      constexpr int IPR = PPR * 4;           // items per pooled row
+      constexpr int NIT = (3 * IPR + CONV_THREADS - 1) / CONV_THREADS;
+      const int Hp = (Hi - 8) >> 1, Wp = (Wi - 8) >> 1;
+      const int pr0 = (ho0 >> 1) - 2;
+      uint4 gq[NIT];
+      uint2 mq[NIT];
+#pragma unroll
+      for (int i = 0; i < NIT; ++i) {
+        const int it = threadIdx.x + i * CONV_THREADS;
+        const int k = it / IPR;
+        const int rem = it - k * IPR;
+        const int pr = pr0 + k;
+        const int wp = (rem >> 2) - 2;
+        // (predicated loads: a branch-free form that loads a clamped
+        // address for border items measured 0.01 ms/step slower)
+        gq[i] = make_uint4(0u, 0u, 0u, 0u);
+        mq[i] = make_uint2(~0u, ~0u);
+        if (k < 3 && pr >= 0 && pr < Hp && wp >= 0 && wp < Wp) {
+          const long long v =
+              ((n * Hp + pr) * (long long)Wp + wp) * 4 + (rem & 3);
+          gq[i] = reinterpret_cast<const uint4*>(in)[v];
+          mq[i] = reinterpret_cast<const uint2*>(mask)[v];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NIT; ++i) {
+        const int it = threadIdx.x + i * CONV_THREADS;
+        const int k = it / IPR;
+        const int rem = it - k * IPR;
+        const int pp = rem >> 2;
+        const int sub = (rem & 3) ^ ((pp >> 1) & 3);
+        if (k < 3) {
+#pragma unroll
+          for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx)
+              *reinterpret_cast<uint4*>(lds_all + (2 * k + dy) * ARPB +
+                                        (2 * pp + dx) * 64 + sub * 16) =
+                  unpool_select(gq[i], mq[i], dy * 2 + dx);
+        }
+      }
+    }
+    const int nstage = UNPOOL ? 0 : (nrows + 4) * NCHA;
+    for (int t = wid; t < nstage; t += 4) {
       const int ir = t / NCHA;
       const int c = t - ir * NCHA;
       const int slot = c * 64 + lane;
@@ -843,7 +907,7 @@ int geops_conv5_nhwc(const bf16_t* in, const bf16_t* w_frags,
   if (pad == PAD_ && need <= PIX_) {                                      \
     hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, PAD_>), dim3(n_wg), \
                        dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,  \
-                       Nn, Hi, Wi, Ho, Wo);                               \
+                       Nn, Hi, Wi, Ho, Wo, (const uint8_t*)nullptr);      \
     return 0;                                                             \
   }
     LDSLAUNCH(120, 4) LDSLAUNCH(232, 4) LDSLAUNCH(120, 0) LDSLAUNCH(232, 0)
@@ -858,6 +922,37 @@ int geops_conv5_nhwc(const bf16_t* in, const bf16_t* w_frags,
   }
   LAUNCH(4, 1) LAUNCH(16, 2) LAUNCH(16, 1) LAUNCH(32, 1) LAUNCH(32, 2)
 #undef LAUNCH
+  return -1;
+}
+
+// conv2 data gradient straight from the POOLED grad_out + argmax mask:
+// the pad == 4 LDS route of geops_conv5_nhwc (CI=32, CO=16, same width
+// table) with the max-pool backward done while staging. Hi/Wi count the
+// full-resolution grad_out plus the virtual 4-pixel border, Ho/Wo are
+// the output; gp/mask are [N][(Hi-8)/2][(Wi-8)/2][32]. Returns 0, or -1
+// for unsupported geometry (odd full-resolution sizes included).
+int geops_conv5_dgrad_unpool_nhwc(const bf16_t* gp, const uint8_t* mask,
+                                  const bf16_t* w_frags, bf16_t* out,
+                                  int Nn, int Hi, int Wi, int Ho, int Wo,
+                                  int CI, int CO, hipStream_t s) {
+  if (CI != 32 || CO != 16 || !mask) return -1;
+  if (Hi < 10 || Wi < 10 || Ho != Hi - 4 || Wo != Wi - 4 ||
+      ((Hi | Wi) & 1))
+    return -1;
+  const int W16 = (Wo + 15) >> 4;
+  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
+  long long prows = (long long)Nn * ((Ho + 1) / 2);
+  int n_wg = (int)((prows < 4096) ? prows : 4096);
+#define UNPLAUNCH(PIX_)                                                   \
+  if (need <= PIX_) {                                                     \
+    hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, 4, true>),          \
+                       dim3(n_wg), dim3(CONV_THREADS), 0, s, gp, w_frags, \
+                       (const float*)nullptr, out, Nn, Hi, Wi, Ho, Wo,    \
+                       mask);                                             \
+    return 0;                                                             \
+  }
+  UNPLAUNCH(120) UNPLAUNCH(232)
+#undef UNPLAUNCH
   return -1;
 }
 

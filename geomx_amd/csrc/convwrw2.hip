@@ -12,7 +12,11 @@
 //     gout), so staging is pure LDS-DMA (__builtin_amdgcn_global_load_lds,
 //     16 B/lane): zero VALU work, zero ds_write instructions. Lanes whose
 //     pixel falls in the zero-padding read a device zero page, so padding
-//     is zero-filled in the same pass.
+//     is zero-filled in the same pass. The UNPOOL variants (backward of
+//     a fused conv+pool stage) instead build the gout image from the
+//     POOLED gradient and the argmax mask: one 16 B + 8 B load per
+//     8 channels of a pooled pixel, four select + ds_write_b128 — the
+//     full-resolution gradient never exists in HBM.
 //   * MFMA fragments come from ds_read_b64_tr_b16 (gfx950's LDS
 //     transpose read, cdna_hip_programming.md T10): each 16-lane group
 //     reads one 4(pix)x16(chan) row-major tile — lane g supplies
@@ -31,6 +35,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "unpool.h"
 
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
@@ -59,12 +65,14 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
                                void*)p;
 }
 
-template <int COT, int PIX>
+template <int COT, int PIX, bool UNPOOL = false>
 __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
     const bf16_t* __restrict__ in,    // [N][Hi][Wi][16]
-    const bf16_t* __restrict__ gout,  // [N][Ho][Wo][CO]
+    const bf16_t* __restrict__ gout,  // [N][Ho][Wo][CO]; UNPOOL: the
+                                      // pooled [N][Ho/2][Wo/2][CO]
     float* __restrict__ part,         // [nWG][T16][CO]
-    int Nn, int Hi, int Wi, int Ho, int Wo) {
+    int Nn, int Hi, int Wi, int Ho, int Wo,
+    const uint8_t* __restrict__ mask) {  // UNPOOL: argmax codes, as gout
   constexpr int CI = 16;
   constexpr int CO = COT * 16;
   constexpr int NT = 25;                 // tap tiles = (kh,kw) pairs
@@ -129,8 +137,55 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
                                                       c * 1024),
             16, 0, 0);
       }
+      if constexpr (UNPOOL) {
+        // gout rows from the POOLED gradient + argmax mask (Ho, Wo
+        // even, so the block's 2 rows are pooled row bh): item `it` is
+        // one 16 B granule (8 channels) of pooled pixel wp, contiguous
+        // in global memory, and expands to its 4 full-resolution
+        // positions. Items past the row (wp >= Wo/2) write the zero
+        // tail [Wo, 32*W) the K windows read. Loads first, then the
+        // selects and ds_writes.
+        constexpr int GV = CO / 8;
+        constexpr int WMAX = (PIX - 4) / 32;
+        constexpr int NIT = (16 * WMAX * GV + WRW2_THREADS - 1) /
+                            WRW2_THREADS;
+        const int nit = 16 * W * GV;
+        const int nreal = (Wo >> 1) * GV;
+        const long long rowv =
+            (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * GV;
+        uint4 gq[NIT];
+        uint2 mq[NIT];
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+          const int it = threadIdx.x + i * WRW2_THREADS;
+          gq[i] = make_uint4(0u, 0u, 0u, 0u);
+          mq[i] = make_uint2(~0u, ~0u);
+          if (it < nreal) {
+            gq[i] = reinterpret_cast<const uint4*>(gout)[rowv + it];
+            mq[i] = reinterpret_cast<const uint2*>(mask)[rowv + it];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+          const int it = threadIdx.x + i * WRW2_THREADS;
+          if (it < nit) {
+            const int wp = it / GV;
+            const int rem = it - wp * GV;
+            const int ot = rem >> 1;
+            const int half = rem & 1;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+              for (int dx = 0; dx < 2; ++dx)
+                *reinterpret_cast<uint4*>(
+                    lds_all + (NROW_IN + dy * COT + ot) * RPB +
+                    (2 * wp + dx) * 32 + half * 16) =
+                    unpool_select(gq[i], mq[i], dy * 2 + dx);
+          }
+        }
+      }
       // gout rows: global [pix][CO] -> per-o-tile LDS [pix][16]
-      const int nchunks_b = nrows * COT * NCH;
+      const int nchunks_b = UNPOOL ? 0 : nrows * COT * NCH;
       for (int t = wid; t < nchunks_b; t += 4) {
         const int rr = t / (COT * NCH);
         const int rem = t - rr * (COT * NCH);
@@ -303,12 +358,14 @@ __global__ void k_tr16_probe(const bf16_t* __restrict__ in,
 // does the interleave, dest stays lane-linear).
 // ---------------------------------------------------------------------
 
-template <int PIX>
+template <int PIX, bool UNPOOL = false>
 __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
     const bf16_t* __restrict__ in,    // [N][Hi][Wi][4]
-    const bf16_t* __restrict__ gout,  // [N][Ho][Wo][16]
+    const bf16_t* __restrict__ gout,  // [N][Ho][Wo][16]; UNPOOL: the
+                                      // pooled [N][Ho/2][Wo/2][16]
     float* __restrict__ part,         // [nWG][176][16]
-    int Nn, int Hi, int Wi, int Ho, int Wo) {
+    int Nn, int Hi, int Wi, int Ho, int Wo,
+    const uint8_t* __restrict__ mask) {  // UNPOOL: argmax codes, as gout
   // v3: the transpose read gathers PER-LANE 8B quarters (verified by
   // test_tr16_per_lane_gather: out[m][j] = mem[addr[4j+(m>>2)] +
   // (m&3) elems]), so the A fragment (lane m = kho*4+ci) reads STRAIGHT
@@ -375,7 +432,35 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
                                                       c * 1024),
             16, 0, 0);
       }
-      const int nchunks_b = nrows * NCHB;
+      if constexpr (UNPOOL) {
+        // both gout rows from pooled row bh + its argmax mask, exactly
+        // as in k_conv5_wrw16_nhwc (one o-tile; at most one item per
+        // thread: 16 * 7 windows * 2 granules = 224)
+        static_assert(16 * ((PIX - 4) / 32) * 2 <= WRW2_THREADS, "");
+        const int it = threadIdx.x;
+        const int nit = 16 * W * 2;
+        const int nreal = (Wo >> 1) * 2;
+        const long long rowv =
+            (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * 2;
+        uint4 gq = make_uint4(0u, 0u, 0u, 0u);
+        uint2 mq = make_uint2(~0u, ~0u);
+        if (it < nreal) {
+          gq = reinterpret_cast<const uint4*>(gout)[rowv + it];
+          mq = reinterpret_cast<const uint2*>(mask)[rowv + it];
+        }
+        if (it < nit) {
+          const int wp = it >> 1;
+          const int half = it & 1;
+#pragma unroll
+          for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx)
+              *reinterpret_cast<uint4*>(lds_all + BOFF + dy * BRPB +
+                                        (2 * wp + dx) * 32 + half * 16) =
+                  unpool_select(gq, mq, dy * 2 + dx);
+        }
+      }
+      const int nchunks_b = UNPOOL ? 0 : nrows * NCHB;
       for (int t = wid; t < nchunks_b; t += 4) {
         const int rr = t / NCHB;
         const int c = t - rr * NCHB;
@@ -490,17 +575,28 @@ __global__ void k_tr16_probe2(const bf16_t* __restrict__ in,
 
 extern "C" {
 
-int geops_conv5_wrw16_nhwc(const bf16_t* in, const bf16_t* gout, float* part,
-                           int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
-                           int CO, int n_wg, hipStream_t s) {
+// Launch tables. `mask` == nullptr: gout is the full-resolution
+// gradient. Otherwise gout is the POOLED gradient [N][Ho/2][Wo/2][CO]
+// and mask its argmax codes; the kernels unpool while staging (Ho, Wo
+// are still the full-resolution sizes and must be even).
+static int wrw16_launch(const bf16_t* in, const bf16_t* gout,
+                        const uint8_t* mask, float* part, int Nn, int Hi,
+                        int Wi, int Ho, int Wo, int CI, int CO, int n_wg,
+                        hipStream_t s) {
   if (CI != 16) return -1;
+  if (mask && ((Ho | Wo) & 1)) return -1;
   const int W = (Wo + 31) >> 5;
   const int need = (W * 32 + 4) > Wi ? (W * 32 + 4) : Wi;
 #define W2LAUNCH(COT_, PIX_)                                              \
   if (need <= PIX_) {                                                     \
-    hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_>), dim3(n_wg),      \
-                       dim3(WRW2_THREADS), 0, s, in, gout, part, Nn, Hi,  \
-                       Wi, Ho, Wo);                                       \
+    if (mask)                                                             \
+      hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, true>),          \
+                         dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout,  \
+                         part, Nn, Hi, Wi, Ho, Wo, mask);                 \
+    else                                                                  \
+      hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, false>),         \
+                         dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout,  \
+                         part, Nn, Hi, Wi, Ho, Wo, mask);                 \
     return n_wg;                                                          \
   }
   if (CO == 32) { W2LAUNCH(2, 136) W2LAUNCH(2, 232) }
@@ -509,23 +605,54 @@ int geops_conv5_wrw16_nhwc(const bf16_t* in, const bf16_t* gout, float* part,
   return -1;
 }
 
-int geops_conv5_wrw4_nhwc(const bf16_t* in, const bf16_t* gout, float* part,
-                          int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
-                          int CO, int n_wg, hipStream_t s) {
+static int wrw4_launch(const bf16_t* in, const bf16_t* gout,
+                       const uint8_t* mask, float* part, int Nn, int Hi,
+                       int Wi, int Ho, int Wo, int CI, int CO, int n_wg,
+                       hipStream_t s) {
   // Wi must be even: the A staging copies 2-pixel (16B) granules
   if (CI != 4 || CO != 16 || (Wi & 1)) return -1;
+  if (mask && ((Ho | Wo) & 1)) return -1;
   const int W = (Wo + 31) >> 5;
   const int need = (W * 32 + 4) > Wi ? (W * 32 + 4) : Wi;
 #define W4LAUNCH(PIX_)                                                    \
   if (need <= PIX_) {                                                     \
-    hipLaunchKernelGGL((k_conv5_wrw4_nhwc<PIX_>), dim3(n_wg),             \
-                       dim3(WRW2_THREADS), 0, s, in, gout, part, Nn, Hi,  \
-                       Wi, Ho, Wo);                                       \
+    if (mask)                                                             \
+      hipLaunchKernelGGL((k_conv5_wrw4_nhwc<PIX_, true>), dim3(n_wg),     \
+                         dim3(WRW2_THREADS), 0, s, in, gout, part, Nn,    \
+                         Hi, Wi, Ho, Wo, mask);                           \
+    else                                                                  \
+      hipLaunchKernelGGL((k_conv5_wrw4_nhwc<PIX_, false>), dim3(n_wg),    \
+                         dim3(WRW2_THREADS), 0, s, in, gout, part, Nn,    \
+                         Hi, Wi, Ho, Wo, mask);                           \
     return n_wg;                                                          \
   }
   W4LAUNCH(136) W4LAUNCH(232)
 #undef W4LAUNCH
   return -1;
+}
+
+int geops_conv5_wrw16_nhwc(const bf16_t* in, const bf16_t* gout, float* part,
+                           int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
+                           int CO, int n_wg, hipStream_t s) {
+  return wrw16_launch(in, gout, nullptr, part, Nn, Hi, Wi, Ho, Wo, CI, CO,
+                      n_wg, s);
+}
+
+int geops_conv5_wrw4_nhwc(const bf16_t* in, const bf16_t* gout, float* part,
+                          int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
+                          int CO, int n_wg, hipStream_t s) {
+  return wrw4_launch(in, gout, nullptr, part, Nn, Hi, Wi, Ho, Wo, CI, CO,
+                     n_wg, s);
+}
+
+// gp/mask: pooled gradient + argmax codes; Ho, Wo full resolution (even)
+int geops_conv5_wrw_unpool_nhwc(const bf16_t* in, const bf16_t* gp,
+                                const uint8_t* mask, float* part, int Nn,
+                                int Hi, int Wi, int Ho, int Wo, int CI,
+                                int CO, int n_wg, hipStream_t s) {
+  if (!mask) return -1;
+  return (CI == 4 ? wrw4_launch : wrw16_launch)(in, gp, mask, part, Nn, Hi,
+                                                Wi, Ho, Wo, CI, CO, n_wg, s);
 }
 
 void geops_tr16_probe(const bf16_t* in, bf16_t* out, hipStream_t s) {

@@ -73,6 +73,13 @@ int geops_conv5_wrw16_nhwc(const unsigned short*, const unsigned short*,
 int geops_conv5_wrw4_nhwc(const unsigned short*, const unsigned short*,
                           float*, int, int, int, int, int, int, int, int,
                           hipStream_t);
+int geops_conv5_wrw_unpool_nhwc(const unsigned short*, const unsigned short*,
+                                const uint8_t*, float*, int, int, int, int,
+                                int, int, int, int, hipStream_t);
+int geops_conv5_dgrad_unpool_nhwc(const unsigned short*, const uint8_t*,
+                                  const unsigned short*, unsigned short*,
+                                  int, int, int, int, int, int, int,
+                                  hipStream_t);
 void geops_tr16_probe(const unsigned short*, unsigned short*, hipStream_t);
 void geops_tr16_probe2(const unsigned short*, const int*, unsigned short*,
                        hipStream_t);
@@ -339,6 +346,65 @@ void conv5_wrw_nhwc(torch::Tensor in, torch::Tensor gout, torch::Tensor part,
   launch_check("conv5_wrw_nhwc");
 }
 
+// Weight gradient from the POOLED grad_out `gp` [N][Ho/2][Wo/2][CO] and
+// its argmax codes `mask`: the kernel does the max-pool backward while
+// staging. Ho, Wo are the full-resolution sizes (even); slab layout and
+// n_wg as conv5_wrw_nhwc.
+void conv5_wrw_unpool_nhwc(torch::Tensor in, torch::Tensor gp,
+                           torch::Tensor mask, torch::Tensor part, int64_t N,
+                           int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
+                           int64_t CI, int64_t CO, int64_t n_wg) {
+  TORCH_CHECK(in.is_cuda() && gp.is_cuda() && mask.is_cuda() &&
+              part.is_cuda());
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16 &&
+              gp.scalar_type() == torch::kBFloat16 &&
+              mask.scalar_type() == torch::kUInt8 &&
+              part.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(Ho == Hi - 4 && Wo == Wi - 4 && in.numel() == N * Hi * Wi * CI,
+              "conv5_wrw_unpool_nhwc: input size mismatch");
+  TORCH_CHECK(gp.numel() == N * (Ho / 2) * (Wo / 2) * CO &&
+                  mask.numel() == gp.numel(),
+              "conv5_wrw_unpool_nhwc: pooled gradient / mask size mismatch");
+  TORCH_CHECK(n_wg > 0 && part.numel() >= n_wg * (CI == 4 ? 176 : 416) * CO,
+              "conv5_wrw_unpool_nhwc: partial slab too small");
+  const int rc = geops_conv5_wrw_unpool_nhwc(
+      (const unsigned short*)in.data_ptr(),
+      (const unsigned short*)gp.data_ptr(), mask.data_ptr<uint8_t>(),
+      part.data_ptr<float>(), (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo,
+      (int)CI, (int)CO, (int)n_wg, cur_stream());
+  TORCH_CHECK(rc > 0, "conv5_wrw_unpool_nhwc: unsupported geometry CI=", CI,
+              " CO=", CO, " Wi=", Wi, " Ho=", Ho, " Wo=", Wo);
+  launch_check("conv5_wrw_unpool_nhwc");
+}
+
+// conv2 data gradient from the POOLED grad_out + argmax codes; sizes as
+// conv5_nhwc with pad=4 (Hi, Wi = full-resolution grad_out + 8).
+void conv5_dgrad_unpool_nhwc(torch::Tensor gp, torch::Tensor mask,
+                             torch::Tensor w_frags, torch::Tensor out,
+                             int64_t N, int64_t Hi, int64_t Wi, int64_t Ho,
+                             int64_t Wo, int64_t CI, int64_t CO) {
+  TORCH_CHECK(gp.is_cuda() && mask.is_cuda() && w_frags.is_cuda() &&
+              out.is_cuda());
+  TORCH_CHECK(gp.scalar_type() == torch::kBFloat16 &&
+              mask.scalar_type() == torch::kUInt8 &&
+              w_frags.scalar_type() == torch::kBFloat16 &&
+              out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(Hi >= 10 && Wi >= 10 &&
+                  gp.numel() == N * ((Hi - 8) / 2) * ((Wi - 8) / 2) * CI &&
+                  mask.numel() == gp.numel(),
+              "conv5_dgrad_unpool_nhwc: pooled gradient / mask size mismatch");
+  TORCH_CHECK(out.numel() == N * Ho * Wo * CO,
+              "conv5_dgrad_unpool_nhwc: output size mismatch");
+  const int rc = geops_conv5_dgrad_unpool_nhwc(
+      (const unsigned short*)gp.data_ptr(), mask.data_ptr<uint8_t>(),
+      (const unsigned short*)w_frags.data_ptr(),
+      (unsigned short*)out.data_ptr(), (int)N, (int)Hi, (int)Wi, (int)Ho,
+      (int)Wo, (int)CI, (int)CO, cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_dgrad_unpool_nhwc: unsupported geometry CI=",
+              CI, " CO=", CO, " Hi=", Hi, " Wi=", Wi);
+  launch_check("conv5_dgrad_unpool_nhwc");
+}
+
 void pad_ch3to4_nhwc(torch::Tensor in, torch::Tensor out, int64_t npix) {
   TORCH_CHECK(in.is_cuda() && out.is_cuda());
   TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
@@ -449,6 +515,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
   m.def("conv5_wrw_nhwc", &conv5_wrw_nhwc);
+  m.def("conv5_wrw_unpool_nhwc", &conv5_wrw_unpool_nhwc);
+  m.def("conv5_dgrad_unpool_nhwc", &conv5_dgrad_unpool_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
   m.def("tr16_probe2", [](torch::Tensor in, torch::Tensor addr,
                           torch::Tensor out) {

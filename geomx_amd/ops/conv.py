@@ -11,6 +11,10 @@ alone (plan_conv5):
     physically padded grad_out for the other supported shapes.
   * weight+bias gradients: ds_read_b64_tr_b16 fragment kernels
     (convwrw2.hip) with the bias fused as an all-ones tap tile.
+Behind a fused-pool forward the wrw and lds_pad4 kernels take the
+pooled gradient and the argmax mask as they are (unpool_fusable) and do
+the max-pool backward while staging; no full-resolution gradient is
+built unless another route needs it.
 Whatever no kernel serves goes to ATen (same math, library kernels);
 one op on ATen does not move the other two off the custom kernels.
 """
@@ -125,20 +129,26 @@ def build_wrw_unpack_index(weight_shape):
 
 def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
                    unpack_idx: torch.Tensor, T16: int, weight_shape,
-                   want_bias: bool = False):
+                   want_bias: bool = False, mask: torch.Tensor = None):
     """Run the custom wrw kernel; returns dW in OIHW fp32 (and, with
     want_bias, the bias gradient the kernel fused via its all-ones tap
-    tile — slab row T16-16)."""
+    tile — slab row T16-16). With `mask`, `go` is the max-POOLED
+    gradient and mask its argmax codes: the kernel unpools while
+    staging (same slabs, same sums, bit-identical result)."""
     from geomx_amd import _geops
     N, CI, Hi, Wi = xb_padded.shape
     CO = go.shape[1]
-    Ho, Wo = go.shape[2], go.shape[3]
+    Ho, Wo = (Hi - 4, Wi - 4) if mask is not None else go.shape[2:]
     n_blocks = N * ((Ho + 3) // 4)
     n_wg = min(_WRW_NWG, n_blocks)
     part = torch.zeros(n_wg, T16, CO, dtype=torch.float32,
                        device=go.device)
-    _geops.conv5_wrw_nhwc(xb_padded, go, part, N, Hi, Wi, Ho, Wo, CI, CO,
-                          n_wg)
+    if mask is not None:
+        _geops.conv5_wrw_unpool_nhwc(xb_padded, go, mask, part, N, Hi, Wi,
+                                     Ho, Wo, CI, CO, n_wg)
+    else:
+        _geops.conv5_wrw_nhwc(xb_padded, go, part, N, Hi, Wi, Ho, Wo, CI,
+                              CO, n_wg)
     full = part.sum(dim=0)
     dw = full.reshape(-1)[unpack_idx].reshape(weight_shape)
     if want_bias:
@@ -266,10 +276,55 @@ def _empty_nhwc(N, C, H, W, device) -> torch.Tensor:
                        memory_format=torch.channels_last)
 
 
-def _dgrad(route, go, x_real, weight, idx):
-    """grad_x of the conv from grad_out `go` (NHWC bf16)."""
+Conv5Unpool = namedtuple("Conv5Unpool", "dgrad wrw")
+
+
+def unpool_fusable(plan: Conv5Plan) -> Conv5Unpool:
+    """Which backward ops of a fwd='pool' stage take the POOLED grad_out
+    plus the argmax mask directly (their kernels do the max-pool
+    backward while staging gout into LDS). Every other route reads the
+    full-resolution gradient relu_maxpool2_bwd scatters."""
+    return Conv5Unpool(dgrad=plan.dgrad == "lds_pad4",
+                       wrw=plan.wrw in ("wrw4", "wrw16"))
+
+
+def _pooled_backward(fuse: Conv5Unpool, need_x: bool, need_w: bool, gp,
+                     mask, scatter, dgrad, wrw):
+    """Backward of a fused-pool stage. `dgrad(go, mask)` / `wrw(go,
+    mask)` run one consumer, on the pooled gradient when given a mask
+    and on the full-resolution one when mask is None. `scatter()` builds
+    the full-resolution gradient; it runs at most once, and only when a
+    needed consumer cannot take the pooled form."""
+    full = []
+
+    def go_full():
+        if not full:
+            full.append(scatter())
+        return full[0]
+
+    grad_x = grad_wb = None
+    if need_x:
+        grad_x = dgrad(gp, mask) if fuse.dgrad else dgrad(go_full(), None)
+    if need_w:
+        grad_wb = wrw(gp, mask) if fuse.wrw else wrw(go_full(), None)
+    return grad_x, grad_wb
+
+
+def _dgrad(route, go, x_real, weight, idx, mask=None):
+    """grad_x of the conv from grad_out `go` (NHWC bf16); with `mask`
+    (route 'lds_pad4' only) `go` is the pooled gradient."""
     N, CIr, Hi, Wi = x_real.shape
-    CO, Ho, Wo = go.shape[1:]
+    CO = go.shape[1]
+    Ho, Wo = Hi - 4, Wi - 4
+    if mask is not None:
+        assert route == "lds_pad4", route
+        from geomx_amd import _geops
+        COp = (CIr + 15) & ~15
+        gx = _empty_nhwc(N, COp, Hi, Wi, go.device)
+        _geops.conv5_dgrad_unpool_nhwc(go, mask, _w_frags(weight, idx.dgrad),
+                                       gx, N, Ho + 8, Wo + 8, Hi, Wi, CO,
+                                       COp)
+        return gx[:, :CIr] if COp != CIr else gx
     if route == "aten":
         return torch.ops.aten.convolution_backward(
             go, x_real, weight.detach().to(torch.bfloat16), None, [1, 1],
@@ -291,16 +346,18 @@ def _dgrad(route, go, x_real, weight, idx):
     return gx[:, :CIr] if COp != CIr else gx
 
 
-def _wrw(route, go, xb, x_real, weight, idx, has_bias):
-    """(grad_w, grad_b) in the weight's dtype; grad_b None without bias."""
+def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None):
+    """(grad_w, grad_b) in the weight's dtype; grad_b None without bias.
+    With `mask` (custom routes only) `go` is the pooled gradient."""
     if route == "aten":
+        assert mask is None
         _, gw, gb = torch.ops.aten.convolution_backward(
             go, x_real, weight.detach().to(torch.bfloat16),
             [weight.shape[0]] if has_bias else None, [1, 1], [0, 0],
             [1, 1], False, [0, 0], 1, [False, True, has_bias])
     else:
         gw, gb = wrw_via_kernel(xb, go, idx.wrw, idx.t16, weight.shape,
-                                want_bias=True)
+                                want_bias=True, mask=mask)
     return (gw.to(weight.dtype),
             gb.to(weight.dtype) if has_bias else None)
 
@@ -316,9 +373,10 @@ def _out_dtype(x: torch.Tensor) -> torch.dtype:
 class _Conv5Fn(torch.autograd.Function):
     """One conv stage under a Conv5Plan. fwd='pool' is conv5 + bias +
     ReLU + 2x2 maxpool in ONE kernel: the full-resolution conv output
-    (1.55 GB at the bench shape) never exists, and backward first
-    scatters grad through the recorded argmax-quadrant mask
-    (relu_maxpool2_bwd). fwd='aten' with a custom wrw is the split
+    (1.55 GB at the bench shape) never exists, and in backward the wrw
+    and lds_pad4 kernels read the pooled gradient through the recorded
+    argmax-quadrant mask (unpool_fusable); the other routes get it
+    scattered to full resolution first (relu_maxpool2_bwd). fwd='aten' with a custom wrw is the split
     backward (0.21 ms vs the 1.61 ms igemm MIOpen picks in-step).
     With `pooled`, fwd='aten' returns the conv in fp32: the fused kernel
     argmaxes its fp32 accumulators, and the eager ReLU + max-pool that
@@ -375,19 +433,37 @@ class _Conv5Fn(torch.autograd.Function):
         x_real = xb[:, :ctx.CIr]
         go = grad_out.to(torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
+        need_x = ctx.needs_input_grad[0]
+        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and
+                                             ctx.needs_input_grad[2])
+
+        def dgrad(g, m):
+            return _dgrad(plan.dgrad, g, x_real, weight, idx, m)
+
+        def wrw(g, m):
+            return _wrw(plan.wrw, g, xb, x_real, weight, idx, ctx.has_bias,
+                        m)
+
         if mask is not None:
-            from geomx_amd import _geops
-            N, _, Hi, Wi = xb.shape
-            CO = weight.shape[0]
-            gp, go = go, _empty_nhwc(N, CO, Hi - 4, Wi - 4, go.device)
-            _geops.relu_maxpool2_bwd(gp, mask, go, N, CO, Hi - 4, Wi - 4)
-        grad_x = grad_w = grad_b = None
-        if ctx.needs_input_grad[0]:
-            grad_x = _dgrad(plan.dgrad, go, x_real, weight, idx)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and
-                                       ctx.needs_input_grad[2]):
-            grad_w, grad_b = _wrw(plan.wrw, go, xb, x_real, weight, idx,
-                                  ctx.has_bias)
+            # fused-pool stage: `go` is the pooled gradient. The wrw and
+            # lds_pad4 kernels unpool it while staging; only a consumer
+            # on another route gets the scattered full-resolution tensor
+            def scatter():
+                from geomx_amd import _geops
+                N, _, Hi, Wi = xb.shape
+                CO = weight.shape[0]
+                full = _empty_nhwc(N, CO, Hi - 4, Wi - 4, go.device)
+                _geops.relu_maxpool2_bwd(go, mask, full, N, CO, Hi - 4,
+                                         Wi - 4)
+                return full
+
+            grad_x, grad_wb = _pooled_backward(
+                unpool_fusable(plan), need_x, need_w, go, mask, scatter,
+                dgrad, wrw)
+        else:
+            grad_x = dgrad(go, None) if need_x else None
+            grad_wb = wrw(go, None) if need_w else None
+        grad_w, grad_b = grad_wb if grad_wb is not None else (None, None)
         return grad_x, grad_w, grad_b, None, None, None
 
 
