@@ -1,7 +1,8 @@
 // Torch bindings for the geomx_amd gfx950 kernel library: kernels.hip
 // (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
-// (5x5 conv forward / data gradient) and convwrw2.hip (5x5 conv weight
-// gradient, tr16 probes).
+// (5x5 conv forward / data gradient), convwrw2.hip (5x5 conv weight
+// gradient, tr16 probes) and fc.hip (NHWC-native first dense layer
+// layout kernels: permuting weight casts, transposing flatten).
 //
 // Thin checked wrappers: dtype/contiguity/device checks, stream plumbing
 // (kernels run on the current torch stream so they order correctly with
@@ -80,6 +81,12 @@ int geops_conv5_dgrad_unpool_nhwc(const unsigned short*, const uint8_t*,
                                   const unsigned short*, unsigned short*,
                                   int, int, int, int, int, int, int,
                                   hipStream_t);
+int geops_fc_w_permute_bf16(const float*, unsigned short*, int, int, int,
+                            hipStream_t);
+int geops_fc_w_unpermute_f32(const unsigned short*, float*, int, int, int,
+                             hipStream_t);
+int geops_fc_flatten_nchw(const unsigned short*, unsigned short*, int, int,
+                          int, hipStream_t);
 void geops_tr16_probe(const unsigned short*, unsigned short*, hipStream_t);
 void geops_tr16_probe2(const unsigned short*, const int*, unsigned short*,
                        hipStream_t);
@@ -405,6 +412,66 @@ void conv5_dgrad_unpool_nhwc(torch::Tensor gp, torch::Tensor mask,
   launch_check("conv5_dgrad_unpool_nhwc");
 }
 
+// ---- first dense layer layout kernels (fc.hip) ----
+
+void check_fc_operand(const torch::Tensor& t, torch::ScalarType dtype,
+                      int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == dtype, name, " has the wrong dtype");
+  TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(),
+              " elements, expected ", numel);
+  // bf16 operands move as 16-byte vectors; the fp32 weight side is
+  // accessed dword-wise (HW may be odd) and needs no more than that
+  if (dtype != torch::kFloat32)
+    TORCH_CHECK(((uintptr_t)t.data_ptr() & 15) == 0, name,
+                " must be 16-byte aligned");
+}
+
+// fp32 master weight [O][C*HW] (NCHW-flatten order) -> bf16 [O][HW*C],
+// the data-gradient GEMM's weight operand.
+torch::Tensor fc_w_permute_bf16(torch::Tensor w, int64_t O, int64_t C,
+                                int64_t HW) {
+  check_fc_operand(w, torch::kFloat32, O * C * HW, "weight");
+  auto wp = torch::empty({O, HW * C}, w.options().dtype(torch::kBFloat16));
+  const int rc = geops_fc_w_permute_bf16(
+      w.data_ptr<float>(), (unsigned short*)wp.data_ptr(), (int)O, (int)C,
+      (int)HW, cur_stream());
+  TORCH_CHECK(rc == 0, "fc_w_permute_bf16: unsupported geometry O=", O,
+              " C=", C, " HW=", HW);
+  launch_check("fc_w_permute_bf16");
+  return wp;
+}
+
+// bf16 [O][HW*C] -> fp32 [O][C*HW]: the inverse, for the weight gradient.
+torch::Tensor fc_w_unpermute_f32(torch::Tensor gp, int64_t O, int64_t C,
+                                 int64_t HW) {
+  check_fc_operand(gp, torch::kBFloat16, O * C * HW, "permuted gradient");
+  auto g = torch::empty({O, C * HW}, gp.options().dtype(torch::kFloat32));
+  const int rc = geops_fc_w_unpermute_f32(
+      (const unsigned short*)gp.data_ptr(), g.data_ptr<float>(), (int)O,
+      (int)C, (int)HW, cur_stream());
+  TORCH_CHECK(rc == 0, "fc_w_unpermute_f32: unsupported geometry O=", O,
+              " C=", C, " HW=", HW);
+  launch_check("fc_w_unpermute_f32");
+  return g;
+}
+
+// channels_last activation [N][HW*C] -> NCHW-flatten order [N][C*HW],
+// bit-exact with torch.flatten(x, 1) of the channels_last tensor.
+torch::Tensor fc_flatten_nchw(torch::Tensor x, int64_t N, int64_t C,
+                              int64_t HW) {
+  check_fc_operand(x, torch::kBFloat16, N * C * HW, "x");
+  auto y = torch::empty({N, C * HW}, x.options());
+  const int rc = geops_fc_flatten_nchw(
+      (const unsigned short*)x.data_ptr(), (unsigned short*)y.data_ptr(),
+      (int)N, (int)C, (int)HW, cur_stream());
+  TORCH_CHECK(rc == 0, "fc_flatten_nchw: unsupported geometry N=", N,
+              " C=", C, " HW=", HW);
+  launch_check("fc_flatten_nchw");
+  return y;
+}
+
 void pad_ch3to4_nhwc(torch::Tensor in, torch::Tensor out, int64_t npix) {
   TORCH_CHECK(in.is_cuda() && out.is_cuda());
   TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
@@ -518,6 +585,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_wrw_unpool_nhwc", &conv5_wrw_unpool_nhwc);
   m.def("conv5_dgrad_unpool_nhwc", &conv5_dgrad_unpool_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
+  m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
+  m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
+  m.def("fc_flatten_nchw", &fc_flatten_nchw);
   m.def("tr16_probe2", [](torch::Tensor in, torch::Tensor addr,
                           torch::Tensor out) {
     TORCH_CHECK(in.is_cuda() && addr.is_cuda() && out.is_cuda());

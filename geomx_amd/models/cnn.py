@@ -20,6 +20,7 @@ class GeoCNN(nn.Module):
                  num_classes: int = 10):
         super().__init__()
         from ..ops.conv import GeoConv5Pool
+        from ..ops.fc import GeoFlattenLinear
         self.features = nn.Sequential(
             # both conv stages: conv+bias+relu+maxpool in ONE gfx950
             # kernel each (no full-resolution conv output in HBM)
@@ -30,8 +31,13 @@ class GeoCNN(nn.Module):
             probe = torch.zeros(1, in_channels, image_size, image_size)
             flat = self.features(probe).numel()
         self.classifier = nn.Sequential(
-            nn.Flatten(),
-            nn.Linear(flat, 256),
+            # slot 0 was nn.Flatten: kept as a parameter-free placeholder
+            # so classifier.1/.3/.5 keep their state-dict names. The
+            # first dense layer takes the 4-D feature map and runs in
+            # its (h, w, c) order (ops/fc.py): no layout copy of the
+            # activation or of its gradient
+            nn.Identity(),
+            GeoFlattenLinear(flat, 256),
             nn.ReLU(inplace=True),
             nn.Linear(256, 128),
             nn.ReLU(inplace=True),
