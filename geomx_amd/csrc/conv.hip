@@ -16,6 +16,9 @@
 //     keeping them out of VGPRs preserves occupancy (the first version
 //     held them in registers: 228 VGPRs -> 2 waves/SIMD, 2x slower
 //     than MIOpen; this version: ~100 VGPRs -> 4-5 waves/SIMD).
+//     The LDS-staged data-gradient kernel (k_conv5_lds_nhwc) is the
+//     exception: its occupancy is set by the LDS row image, so it holds
+//     all 25 fragments in registers and keeps B out of LDS.
 //   C/D: lane l holds out[pixel (l>>4)*4+i][o = l&15], i = 0..3.
 //
 // Each wave owns whole (n, ho) output rows (row-walk: no per-tile
@@ -625,11 +628,32 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool16_nhwc(
 
 
 // LDS-staged DENSE conv for the conv2 data-gradient: CI=32 (the padded
-// grad-out), CO=16 (the dgrad output channels). Same structure as the
-// fused pool16 kernel — block stages its 5 input rows + the weight
-// panel lives in LDS — but writes the full-resolution output (no pool).
+// grad-out), CO=16 (the dgrad output channels), full-resolution output.
+//
+// With CI=32 the row span is S = Sp = 160 = 5 chunks of 32, so chunk km
+// is exactly (kh = km/5, j = km%5) and its A fragment is pixel wo+j of
+// staged row (output row + kh): lane (p, q) holds channels q*8..+8. The
+// fragment (staged row r, j) is therefore the A operand of output row
+// r-kh with weight fragment kh*5+j for EVERY kh in 0..4. A wave's work
+// unit is (16-pixel tile, ROWS=4 output rows): it walks the ROWS+4
+// staged rows top to bottom, reads each row's 5 fragments ONCE and
+// issues up to 5 MFMAs per fragment into the per-output-row
+// accumulators (40 ds_read_b128 per 100 MFMAs; the 2-row kernel before
+// it read one A and one B fragment per MFMA). Each accumulator still
+// receives its 25 MFMAs in ascending km with the fragments of the
+// direct kernel, so the output is bit-identical to k_conv5_nhwc<32,1>.
+//
+// The 25 weight fragments live in REGISTERS (100 VGPRs) for the whole
+// persistent loop: occupancy here is set by the LDS row image, not by
+// registers, and the B panel leaves LDS. The next staged row's
+// fragments are loaded before this row's MFMAs are issued (the walk is
+// fully unrolled, so the compiler places counted lgkmcnt waits). The
+// UNPOOL variants also issue the NEXT block's global loads before the
+// MFMA phase and do the selects + ds_writes after the barrier that
+// ends it, which takes global latency off the critical path.
 template <int CIT, int COT, int PIX, int PAD = 0, bool UNPOOL = false>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
+__global__ __launch_bounds__(CONV_THREADS, (PIX <= 120 ? 2 : 1))
+void k_conv5_lds_nhwc(
     const bf16_t* __restrict__ in,   // [N][Hi-2P][Wi-2P][CI] (P virtual)
     const bf16_t* __restrict__ w_frags,  // [COT][nK][64][8]
     const float* __restrict__ bias,      // [CO] or nullptr
@@ -644,22 +668,18 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
   // staging pass expands each pooled pixel to its 4 full-resolution
   // positions, so LDS holds what the PAD=4 staging of the scattered
   // gradient would
-  static_assert(!UNPOOL || (CIT == 32 && PAD == 4), "conv2 dgrad only");
+  static_assert(CIT == 32 && COT == 1, "conv2 dgrad only");
+  static_assert(!UNPOOL || PAD == 4, "the pooled form has a virtual border");
   constexpr int CI = CIT;
-  constexpr int S = 5 * CI;
-  constexpr int Sp = (S + 7) & ~7;
-  constexpr int K = 5 * Sp;
-  constexpr int nK = (K + 31) / 32;
-  constexpr int CO = COT * 16;
+  constexpr int nK = 25;                 // (kh, j), 5 chunks per tap row
+  constexpr int CO = 16;
   constexpr int AROW_BYTES = PIX * CI * 2;
   constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
   constexpr int ARPB = NCHA * 1024 + 64;
-  constexpr int ROWS = 2;                // output rows per block
+  constexpr int ROWS = 4;                // output rows per block
   constexpr int NROW = ROWS + 4;         // staged input rows
-  constexpr int BBYTES = COT * nK * 64 * 16;
-  __shared__ __attribute__((aligned(128))) char lds_all[NROW * ARPB +
-                                                        BBYTES];
-  constexpr int BOFF = NROW * ARPB;
+  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;  // units per wave
+  __shared__ __attribute__((aligned(128))) char lds_all[NROW * ARPB];
 
   const int lane = threadIdx.x & 63;
   const int p = lane & 15;
@@ -667,14 +687,12 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
   const int m = lane & 15;
   const int wid = threadIdx.x >> 6;
 
-  for (int t = threadIdx.x; t < COT * nK * 64; t += blockDim.x) {
-    reinterpret_cast<uint4*>(lds_all + BOFF)[t] =
-        reinterpret_cast<const uint4*>(w_frags)[t];
-  }
-  float bias_v[COT];
+  // weight fragments: one bf16x8 per (km, lane), held for every block
+  bf16x8 breg[nK];
 #pragma unroll
-  for (int ct = 0; ct < COT; ++ct)
-    bias_v[ct] = bias ? bias[ct * 16 + m] : 0.0f;
+  for (int i = 0; i < nK; ++i)
+    breg[i] = *reinterpret_cast<const bf16x8*>(w_frags + (i * 64 + lane) * 8);
+  const float bias_v = bias ? bias[m] : 0.0f;
 
   const int tiles_w = (Wo + 15) >> 4;
   const int hblocks = (Ho + ROWS - 1) / ROWS;
@@ -683,68 +701,83 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
   const int n_wg = gridDim.x;
   const unsigned lds0 =
       (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_all;
-  const bf16x8* lds_bv =
-      reinterpret_cast<const bf16x8*>(lds_all + BOFF) + lane;
+
+  // UNPOOL staging. Staged row ir is real row ho0 + ir - 4 and staged
+  // pixel pix is real pixel pix - 4, both even-aligned: the 8 rows are
+  // pooled rows (ho0>>1) - 2 + k, k = 0..3, and pixels (2pp, 2pp+1) are
+  // pooled pixel pp - 2. Item `it` = (k, pp, s): channel granule s
+  // (8 channels, 16 B + 8 mask bytes, contiguous in global memory
+  // along (pp, s)) of one pooled pixel, written to its 4 full-
+  // resolution positions under the same XOR swizzle as the LDS-DMA
+  // staging (granule s sits at sub-slot s ^ ((pix>>2)&3), and pix>>2 ==
+  // pp>>1 for both pixels). Items outside the image write the zero
+  // border / tail. unp_load issues the global loads of one block into
+  // registers; unp_write does the selects and ds_writes.
+  constexpr int PPR = NCHA * 8;          // pooled pixels per LDS row
+  constexpr int IPR = PPR * 4;           // items per pooled row
+  constexpr int NPR = NROW / 2;          // pooled rows per block
+  constexpr int NIT =
+      UNPOOL ? (NPR * IPR + CONV_THREADS - 1) / CONV_THREADS : 1;
+  uint4 gq[NIT];
+  uint2 mq[NIT];
+  auto unp_load = [&](long long b) __attribute__((always_inline)) {
+    const int ho0 = (int)(b % hblocks) * ROWS;
+    const long long n = b / hblocks;
+    const int Hp = (Hi - 8) >> 1, Wp = (Wi - 8) >> 1;
+    const int pr0 = (ho0 >> 1) - 2;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int it = threadIdx.x + i * CONV_THREADS;
+      const int k = it / IPR;
+      const int rem = it - k * IPR;
+      const int pr = pr0 + k;
+      const int wp = (rem >> 2) - 2;
+      // (predicated loads: a branch-free form that loads a clamped
+      // address for border items measured 0.01 ms/step slower)
+      gq[i] = make_uint4(0u, 0u, 0u, 0u);
+      mq[i] = make_uint2(~0u, ~0u);
+      if (k < NPR && pr >= 0 && pr < Hp && wp >= 0 && wp < Wp) {
+        const long long v =
+            ((n * Hp + pr) * (long long)Wp + wp) * 4 + (rem & 3);
+        gq[i] = reinterpret_cast<const uint4*>(in)[v];
+        mq[i] = reinterpret_cast<const uint2*>(mask)[v];
+      }
+    }
+  };
+  auto unp_write = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int it = threadIdx.x + i * CONV_THREADS;
+      const int k = it / IPR;
+      const int rem = it - k * IPR;
+      const int pp = rem >> 2;
+      const int sub = (rem & 3) ^ ((pp >> 1) & 3);
+      if (k < NPR) {
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 2; ++dx)
+            *reinterpret_cast<uint4*>(lds_all + (2 * k + dy) * ARPB +
+                                      (2 * pp + dx) * 64 + sub * 16) =
+                unpool_select(gq[i], mq[i], dy * 2 + dx);
+      }
+    }
+  };
+  if constexpr (UNPOOL) {
+    if (wg < n_blocks) {
+      unp_load(wg);
+      unp_write();
+    }
+  }
 
   for (long long blk = wg; blk < n_blocks; blk += n_wg) {
     const int hb = (int)(blk % hblocks);
     const long long n = blk / hblocks;
     const int ho0 = hb * ROWS;
     const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
-    if constexpr (UNPOOL) {
-      // staged row ir is real row ho0 + ir - 4 and staged pixel pix is
-      // real pixel pix - 4, both even-aligned: the 6 rows are pooled
-      // rows (ho0>>1) - 2 + k, k = 0..2, and pixels (2pp, 2pp+1) are
-      // pooled pixel pp - 2. Item `it` = (k, pp, s): channel granule s
-      // (8 channels, 16 B + 8 mask bytes, contiguous in global memory
-      // along (pp, s)) of one pooled pixel, written to its 4 full-
-      // resolution positions under the same XOR swizzle as below
-      // (granule s sits at sub-slot s ^ ((pix>>2)&3), and pix>>2 ==
-      // pp>>1 for both pixels). Items outside the image write the zero
-      // border / tail. Loads first, then the selects and ds_writes.
-      constexpr int PPR = NCHA * 8;          // pooled pixels per LDS row
-      constexpr int IPR = PPR * 4;           // items per pooled row
-      constexpr int NIT = (3 * IPR + CONV_THREADS - 1) / CONV_THREADS;
-      const int Hp = (Hi - 8) >> 1, Wp = (Wi - 8) >> 1;
-      const int pr0 = (ho0 >> 1) - 2;
-      uint4 gq[NIT];
-      uint2 mq[NIT];
-#pragma unroll
-      for (int i = 0; i < NIT; ++i) {
-        const int it = threadIdx.x + i * CONV_THREADS;
-        const int k = it / IPR;
-        const int rem = it - k * IPR;
-        const int pr = pr0 + k;
-        const int wp = (rem >> 2) - 2;
-        // (predicated loads: a branch-free form that loads a clamped
-        // address for border items measured 0.01 ms/step slower)
-        gq[i] = make_uint4(0u, 0u, 0u, 0u);
-        mq[i] = make_uint2(~0u, ~0u);
-        if (k < 3 && pr >= 0 && pr < Hp && wp >= 0 && wp < Wp) {
-          const long long v =
-              ((n * Hp + pr) * (long long)Wp + wp) * 4 + (rem & 3);
-          gq[i] = reinterpret_cast<const uint4*>(in)[v];
-          mq[i] = reinterpret_cast<const uint2*>(mask)[v];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NIT; ++i) {
-        const int it = threadIdx.x + i * CONV_THREADS;
-        const int k = it / IPR;
-        const int rem = it - k * IPR;
-        const int pp = rem >> 2;
-        const int sub = (rem & 3) ^ ((pp >> 1) & 3);
-        if (k < 3) {
-#pragma unroll
-          for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx)
-              *reinterpret_cast<uint4*>(lds_all + (2 * k + dy) * ARPB +
-                                        (2 * pp + dx) * 64 + sub * 16) =
-                  unpool_select(gq[i], mq[i], dy * 2 + dx);
-        }
-      }
-    }
+    // LDS-DMA staging of the rows this block's outputs read; with
+    // nrows < ROWS the rows below keep older data, which only reaches
+    // accumulators that are never stored
     const int nstage = UNPOOL ? 0 : (nrows + 4) * NCHA;
     for (int t = wid; t < nstage; t += 4) {
       const int ir = t / NCHA;
@@ -782,71 +815,115 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_lds_nhwc(
                                                     c * 1024),
           16, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // (the pooled form has no LDS-DMA in flight here, and waiting would
+    // also wait for the previous block's output stores)
+    if constexpr (!UNPOOL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    const long long out_row0 =
-        ((long long)n * Ho + ho0) * (long long)Wo * CO;
-    for (int tw = wid; tw < tiles_w; tw += 4) {
+    // the next block's pooled rows travel while this block computes
+    const bool has_next = UNPOOL && blk + n_wg < n_blocks;
+    if constexpr (UNPOOL) {
+      if (has_next) unp_load(blk + n_wg);
+    }
+
+    // a wave's units are tiles wid, wid+4, ...; their packed outputs
+    // wait in registers (2 per row) until the staging of the next block
+    // is done, so that the wait for the prefetched loads above never
+    // covers a store that was issued after them
+    uint2 pk[MAXU][ROWS] = {};
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      const int tw = wid + 4 * u;
+      if (tw >= tiles_w) break;
       const int wo_raw = (tw << 4) + p;
       const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      f32x4 a0[COT], a1[COT];
+      // chunk j of a staged row is pixel wo+j: granule q under the
+      // staging XOR ((pixel>>2)&3)
+      unsigned aoff[5];
 #pragma unroll
-      for (int ct = 0; ct < COT; ++ct) {
-        a0[ct] = (f32x4)0.0f;
-        a1[ct] = (f32x4)0.0f;
+      for (int j = 0; j < 5; ++j) {
+        const int Pp = wo + j;
+        aoff[j] = lds0 + (unsigned)((Pp * 4 + (q ^ ((Pp >> 2) & 3))) * 16);
       }
-#pragma unroll 1
-      for (int km = 0; km < nK; ++km) {
-        const int k0 = km * 32 + q * 8;
-        const int kh = k0 / Sp;
-        const int j0 = k0 % Sp;
-        bf16x8 f0 = (bf16x8)0, f1 = (bf16x8)0;
-        if (k0 < K && j0 < S) {
-          unsigned off;
-          if (CI == 32) {
-            const int g = j0 >> 3;
-            const int Pp = wo + (g >> 2);
-            off = (unsigned)(((wo * 4 + (g & ~3)) +
-                              ((g & 3) ^ ((Pp >> 2) & 3))) * 16);
-          } else {
-            off = (unsigned)(wo * (CI * 2) + j0 * 2);
-          }
-          if (S - j0 >= 8) {
-            f0 = *(const __attribute__((address_space(3)))
-                   bf16x8*)(uintptr_t)(lds0 + kh * ARPB + off);
-            f1 = *(const __attribute__((address_space(3)))
-                   bf16x8*)(uintptr_t)(lds0 + (kh + 1) * ARPB + off);
+      auto load_row = [&](int r, bf16x8(&dst)[5]) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+          dst[j] = *(const __attribute__((address_space(3)))
+                     bf16x8*)(uintptr_t)(aoff[j] + r * ARPB);
+      };
+      f32x4 acc[ROWS];
+#pragma unroll
+      for (int o = 0; o < ROWS; ++o) acc[o] = (f32x4)0.0f;
+      bf16x8 af[5];
+      load_row(0, af);
+#pragma unroll
+      for (int r = 0; r < NROW; ++r) {
+        bf16x8 afn[5];
+        if (r + 1 < NROW) load_row(r + 1, afn);
+        // staged row r is tap row kh = r - o of output row o; per
+        // accumulator the MFMAs arrive in ascending km = kh*5 + j
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+#pragma unroll
+          for (int o = 0; o < ROWS; ++o) {
+            const int kh = r - o;
+            if (kh >= 0 && kh < 5)
+              acc[o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  af[j], breg[kh * 5 + j], acc[o], 0, 0, 0);
           }
         }
+        if (r + 1 < NROW) {
 #pragma unroll
-        for (int ct = 0; ct < COT; ++ct) {
-          const bf16x8 bf = lds_bv[(ct * nK + km) * 64];
-          a0[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f0, bf, a0[ct],
-                                                           0, 0, 0);
-          a1[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, bf, a1[ct],
-                                                           0, 0, 0);
+          for (int j = 0; j < 5; ++j) af[j] = afn[j];
         }
       }
-      const int wo0 = tw << 4;
-      const bool full = (wo0 + 16 <= Wo);
-      const long long s_base = out_row0 + (long long)wo0 * CO + m;
+      // Lane (q, m) holds pixels q*4+i of channel m. A 4x4 transpose
+      // inside each lane quad (two DPP exchanges on packed bf16 pairs)
+      // gives it channels (m&~3)..+3 of pixel q*4+(m&3): one 8-byte
+      // store, 512 contiguous bytes per wave and row, in place of four
+      // 2-byte stores.
+      const unsigned sel1 = (m & 1) ? 0x03020706u : 0x05040100u;
+      const bool lo2 = (m & 3) < 2;
 #pragma unroll
-      for (int ct = 0; ct < COT; ++ct) {
-        const long long sb = s_base + ct * 16;
+      for (int o = 0; o < ROWS; ++o) {
+        unsigned v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int prow = q * 4 + i;
-          if (full || wo0 + prow < Wo) {
-            out[sb + (long long)prow * CO] = cf2bf(a0[ct][i] + bias_v[ct]);
-            if (nrows > 1)
-              out[sb + (long long)Wo * CO + (long long)prow * CO] =
-                  cf2bf(a1[ct][i] + bias_v[ct]);
-          }
-        }
+        for (int i = 0; i < 4; ++i) v[i] = cf2bf(acc[o][i] + bias_v);
+        const unsigned a = v[0] | (v[1] << 16);
+        const unsigned b = v[2] | (v[3] << 16);
+        // lane^1: a1 / b1 pair element (m&1) / 2+(m&1) of both lanes
+        const unsigned a1 = __builtin_amdgcn_perm(
+            (unsigned)__builtin_amdgcn_mov_dpp((int)a, 0xB1, 0xF, 0xF, true),
+            a, sel1);
+        const unsigned b1 = __builtin_amdgcn_perm(
+            (unsigned)__builtin_amdgcn_mov_dpp((int)b, 0xB1, 0xF, 0xF, true),
+            b, sel1);
+        // lane^2: the lower lane pair keeps a1 and takes the upper
+        // pair's a1 as its channels 2..3; the upper pair mirrors it
+        const unsigned snd = lo2 ? b1 : a1;
+        const unsigned rcv =
+            (unsigned)__builtin_amdgcn_mov_dpp((int)snd, 0x4E, 0xF, 0xF, true);
+        pk[u][o] = make_uint2(lo2 ? a1 : rcv, lo2 ? rcv : b1);
       }
     }
     __syncthreads();
+    if constexpr (UNPOOL) {
+      if (has_next) unp_write();
+    }
+    const long long out_row0 =
+        ((long long)n * Ho + ho0) * (long long)Wo * CO;
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      const int spix = ((wid + 4 * u) << 4) + q * 4 + (m & 3);
+      if (spix < Wo) {
+        const long long sb = out_row0 + (long long)spix * CO + (m & ~3);
+#pragma unroll
+        for (int o = 0; o < ROWS; ++o)
+          if (o < nrows)
+            *reinterpret_cast<uint2*>(out + sb + (long long)o * Wo * CO) =
+                pk[u][o];
+      }
+    }
   }
 }
 
@@ -882,7 +959,83 @@ static inline int conv_blocks(long long rows) {
   return (int)blocks;
 }
 
+// Launch table of k_conv5_lds_nhwc<32, 1, ...> (CI=32, CO=16): staging
+// rows of 120 and 232 pixels, pad 0 / pad 4, and with `mask` the pooled
+// (UNPOOL) form of pad 4. n_wg <= 0 picks the default grid: one
+// workgroup per 4-row block up to 4 resident rounds of 2 (120) or 1
+// (232) workgroups per CU on 256 CUs, so the weight fragments are
+// fetched by few workgroups and the cross-block prefetch has blocks to
+// run ahead of. Returns 0, or -1 when no variant serves the geometry.
+static int conv5_lds_launch(const bf16_t* in, const uint8_t* mask,
+                            const bf16_t* w_frags, const float* bias,
+                            bf16_t* out, int Nn, int Hi, int Wi, int Ho,
+                            int Wo, int pad, int n_wg, hipStream_t s) {
+  const int W16 = (Wo + 15) >> 4;
+  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
+  if (need > 232 || (pad != 0 && pad != 4) || (mask && pad != 4)) return -1;
+  const long long blocks = (long long)Nn * ((Ho + 3) / 4);
+  if (n_wg <= 0) {
+    const long long cap = need <= 120 ? 2048 : 1024;
+    n_wg = (int)(blocks < cap ? blocks : cap);
+  }
+  if (n_wg < 1) n_wg = 1;
+#define LDSLAUNCH(PIX_, PAD_, UNP_)                                        \
+  if (pad == PAD_ && need <= PIX_ && (mask != nullptr) == UNP_) {          \
+    hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, PAD_, UNP_>),        \
+                       dim3(n_wg), dim3(CONV_THREADS), 0, s, in, w_frags,  \
+                       bias, out, Nn, Hi, Wi, Ho, Wo, mask);               \
+    return 0;                                                              \
+  }
+  LDSLAUNCH(120, 4, true) LDSLAUNCH(232, 4, true)
+  LDSLAUNCH(120, 4, false) LDSLAUNCH(232, 4, false)
+  LDSLAUNCH(120, 0, false) LDSLAUNCH(232, 0, false)
+#undef LDSLAUNCH
+  return -1;
+}
+
+// geometry the pooled (UNPOOL) dgrad form accepts
+static bool conv5_unpool_geometry_ok(const uint8_t* mask, int Hi, int Wi,
+                                     int Ho, int Wo, int CI, int CO) {
+  if (CI != 32 || CO != 16 || !mask) return false;
+  return Hi >= 10 && Wi >= 10 && Ho == Hi - 4 && Wo == Wi - 4 &&
+         !((Hi | Wi) & 1);
+}
+
 extern "C" {
+
+// Test hook: ALWAYS the direct kernel k_conv5_nhwc<32, 1> on a
+// physically padded input (Hi = Ho + 4, Wi = Wo + 4). It issues the same
+// MFMA sequence per output as the LDS dgrad kernel, which geops_conv5_nhwc
+// prefers below 236-pixel rows. Returns 0, or -1 for other geometry.
+int geops_conv5_direct_nhwc(const bf16_t* in, const bf16_t* w_frags,
+                            const float* bias, bf16_t* out, int Nn, int Hi,
+                            int Wi, int Ho, int Wo, int CI, int CO,
+                            hipStream_t s) {
+  if (CI != 32 || CO != 16 || Ho < 1 || Wo < 1 || Hi != Ho + 4 ||
+      Wi != Wo + 4)
+    return -1;
+  const dim3 grid(conv_blocks((long long)Nn * Ho)), block(CONV_THREADS);
+  hipLaunchKernelGGL((k_conv5_nhwc<32, 1>), grid, block, 0, s, in, w_frags,
+                     bias, out, Nn, Hi, Wi, Ho, Wo);
+  return 0;
+}
+
+// Test hook: the pad == 4 LDS dgrad (`mask` null: `in` is the full-
+// resolution grad_out) or its pooled form (`mask` set: `in` is the
+// pooled grad_out) on a grid of n_wg workgroups, so that small inputs
+// reach the persistent loop. Same geometry table as the default calls.
+int geops_conv5_dgrad_nwg_nhwc(const bf16_t* in, const uint8_t* mask,
+                               const bf16_t* w_frags, bf16_t* out, int Nn,
+                               int Hi, int Wi, int Ho, int Wo, int CI,
+                               int CO, int n_wg, hipStream_t s) {
+  if (CI != 32 || CO != 16 || n_wg < 1 || Ho != Hi - 4 || Wo != Wi - 4 ||
+      Hi < 10 || Wi < 10)
+    return -1;
+  if (mask && !conv5_unpool_geometry_ok(mask, Hi, Wi, Ho, Wo, CI, CO))
+    return -1;
+  return conv5_lds_launch(in, mask, w_frags, nullptr, out, Nn, Hi, Wi, Ho,
+                          Wo, 4, n_wg, s);
+}
 
 // returns 0 on success, -1 for unsupported geometry
 int geops_conv5_nhwc(const bf16_t* in, const bf16_t* w_frags,
@@ -898,21 +1051,10 @@ int geops_conv5_nhwc(const bf16_t* in, const bf16_t* w_frags,
   // (the conv2 data gradient). The LDS variants are compiled for 120-
   // and 232-pixel staging rows; wider pad-0 rows fall through to the
   // direct kernel, which has no width limit.
-  if (CI == 32 && CO == 16) {
-    const int W16 = (Wo + 15) >> 4;
-    const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
-    long long prows = (long long)Nn * ((Ho + 1) / 2);
-    int n_wg = (int)((prows < 4096) ? prows : 4096);
-#define LDSLAUNCH(PIX_, PAD_)                                             \
-  if (pad == PAD_ && need <= PIX_) {                                      \
-    hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, PAD_>), dim3(n_wg), \
-                       dim3(CONV_THREADS), 0, s, in, w_frags, bias, out,  \
-                       Nn, Hi, Wi, Ho, Wo, (const uint8_t*)nullptr);      \
-    return 0;                                                             \
-  }
-    LDSLAUNCH(120, 4) LDSLAUNCH(232, 4) LDSLAUNCH(120, 0) LDSLAUNCH(232, 0)
-#undef LDSLAUNCH
-  }
+  if (CI == 32 && CO == 16 &&
+      conv5_lds_launch(in, nullptr, w_frags, bias, out, Nn, Hi, Wi, Ho, Wo,
+                       pad, 0, s) == 0)
+    return 0;
   if (pad != 0) return -1;
 #define LAUNCH(CI_, COT_)                                                 \
   if (CI == CI_ && CO == COT_ * 16) {                                     \
@@ -935,27 +1077,10 @@ int geops_conv5_dgrad_unpool_nhwc(const bf16_t* gp, const uint8_t* mask,
                                   const bf16_t* w_frags, bf16_t* out,
                                   int Nn, int Hi, int Wi, int Ho, int Wo,
                                   int CI, int CO, hipStream_t s) {
-  if (CI != 32 || CO != 16 || !mask) return -1;
-  if (Hi < 10 || Wi < 10 || Ho != Hi - 4 || Wo != Wi - 4 ||
-      ((Hi | Wi) & 1))
-    return -1;
-  const int W16 = (Wo + 15) >> 4;
-  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
-  long long prows = (long long)Nn * ((Ho + 1) / 2);
-  int n_wg = (int)((prows < 4096) ? prows : 4096);
-#define UNPLAUNCH(PIX_)                                                   \
-  if (need <= PIX_) {                                                     \
-    hipLaunchKernelGGL((k_conv5_lds_nhwc<32, 1, PIX_, 4, true>),          \
-                       dim3(n_wg), dim3(CONV_THREADS), 0, s, gp, w_frags, \
-                       (const float*)nullptr, out, Nn, Hi, Wi, Ho, Wo,    \
-                       mask);                                             \
-    return 0;                                                             \
-  }
-  UNPLAUNCH(120) UNPLAUNCH(232)
-#undef UNPLAUNCH
-  return -1;
+  if (!conv5_unpool_geometry_ok(mask, Hi, Wi, Ho, Wo, CI, CO)) return -1;
+  return conv5_lds_launch(gp, mask, w_frags, nullptr, out, Nn, Hi, Wi, Ho,
+                          Wo, 4, 0, s);
 }
-
 
 int geops_conv5_pool_nhwc(const bf16_t* in, const bf16_t* w_frags,
                           const float* bias, bf16_t* out, uint8_t* mask,

@@ -81,6 +81,13 @@ int geops_conv5_dgrad_unpool_nhwc(const unsigned short*, const uint8_t*,
                                   const unsigned short*, unsigned short*,
                                   int, int, int, int, int, int, int,
                                   hipStream_t);
+int geops_conv5_direct_nhwc(const unsigned short*, const unsigned short*,
+                            const float*, unsigned short*, int, int, int, int,
+                            int, int, int, hipStream_t);
+int geops_conv5_dgrad_nwg_nhwc(const unsigned short*, const uint8_t*,
+                               const unsigned short*, unsigned short*, int,
+                               int, int, int, int, int, int, int,
+                               hipStream_t);
 int geops_fc_w_permute_bf16(const float*, unsigned short*, int, int, int,
                             hipStream_t);
 int geops_fc_w_unpermute_f32(const unsigned short*, float*, int, int, int,
@@ -412,6 +419,69 @@ void conv5_dgrad_unpool_nhwc(torch::Tensor gp, torch::Tensor mask,
   launch_check("conv5_dgrad_unpool_nhwc");
 }
 
+// Test hook: the direct kernel k_conv5_nhwc<32, 1> on a physically
+// padded input [N][Ho+4][Wo+4][32], whatever the row width. conv5_nhwc
+// routes such rows to the LDS kernel below 236 pixels; this entry is the
+// bit-exact oracle that kernel is tested against.
+void conv5_direct_nhwc(torch::Tensor in, torch::Tensor w_frags,
+                       torch::Tensor out, int64_t N, int64_t Hi, int64_t Wi,
+                       int64_t Ho, int64_t Wo, int64_t CI, int64_t CO) {
+  TORCH_CHECK(in.is_cuda() && w_frags.is_cuda() && out.is_cuda());
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16 &&
+              w_frags.scalar_type() == torch::kBFloat16 &&
+              out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(in.numel() == N * Hi * Wi * CI &&
+                  out.numel() == N * Ho * Wo * CO &&
+                  w_frags.numel() == 25 * 64 * 8,
+              "conv5_direct_nhwc: tensor size mismatch");
+  const int rc = geops_conv5_direct_nhwc(
+      (const unsigned short*)in.data_ptr(),
+      (const unsigned short*)w_frags.data_ptr(), nullptr,
+      (unsigned short*)out.data_ptr(), (int)N, (int)Hi, (int)Wi, (int)Ho,
+      (int)Wo, (int)CI, (int)CO, cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_direct_nhwc: unsupported geometry CI=", CI,
+              " CO=", CO, " Hi=", Hi, " Wi=", Wi);
+  launch_check("conv5_direct_nhwc");
+}
+
+// Test hook: the conv2 data gradient on a grid of n_wg workgroups, so
+// that a small input runs several blocks per workgroup. With an empty
+// `mask`, `in` is the full-resolution grad_out (conv5_nhwc with pad=4);
+// otherwise `in` is the pooled grad_out (conv5_dgrad_unpool_nhwc).
+void conv5_dgrad_nwg_nhwc(torch::Tensor in, torch::Tensor mask,
+                          torch::Tensor w_frags, torch::Tensor out,
+                          int64_t N, int64_t Hi, int64_t Wi, int64_t Ho,
+                          int64_t Wo, int64_t CI, int64_t CO, int64_t n_wg) {
+  const bool pooled = mask.defined() && mask.numel() > 0;
+  TORCH_CHECK(in.is_cuda() && w_frags.is_cuda() && out.is_cuda());
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16 &&
+              w_frags.scalar_type() == torch::kBFloat16 &&
+              out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(Hi >= 10 && Wi >= 10 && n_wg >= 1 && n_wg <= 65536,
+              "conv5_dgrad_nwg_nhwc: bad size or n_wg");
+  if (pooled) {
+    TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8);
+    TORCH_CHECK(in.numel() == N * ((Hi - 8) / 2) * ((Wi - 8) / 2) * CI &&
+                    mask.numel() == in.numel(),
+                "conv5_dgrad_nwg_nhwc: pooled gradient / mask size mismatch");
+  } else {
+    TORCH_CHECK(in.numel() == N * (Hi - 8) * (Wi - 8) * CI,
+                "conv5_dgrad_nwg_nhwc: gradient size mismatch");
+  }
+  TORCH_CHECK(out.numel() == N * Ho * Wo * CO &&
+                  w_frags.numel() == 25 * 64 * 8,
+              "conv5_dgrad_nwg_nhwc: output / weight size mismatch");
+  const int rc = geops_conv5_dgrad_nwg_nhwc(
+      (const unsigned short*)in.data_ptr(),
+      pooled ? mask.data_ptr<uint8_t>() : nullptr,
+      (const unsigned short*)w_frags.data_ptr(),
+      (unsigned short*)out.data_ptr(), (int)N, (int)Hi, (int)Wi, (int)Ho,
+      (int)Wo, (int)CI, (int)CO, (int)n_wg, cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_dgrad_nwg_nhwc: unsupported geometry CI=", CI,
+              " CO=", CO, " Hi=", Hi, " Wi=", Wi);
+  launch_check("conv5_dgrad_nwg_nhwc");
+}
+
 // ---- first dense layer layout kernels (fc.hip) ----
 
 void check_fc_operand(const torch::Tensor& t, torch::ScalarType dtype,
@@ -584,6 +654,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_wrw_nhwc", &conv5_wrw_nhwc);
   m.def("conv5_wrw_unpool_nhwc", &conv5_wrw_unpool_nhwc);
   m.def("conv5_dgrad_unpool_nhwc", &conv5_dgrad_unpool_nhwc);
+  m.def("conv5_direct_nhwc", &conv5_direct_nhwc);
+  m.def("conv5_dgrad_nwg_nhwc", &conv5_dgrad_nwg_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
