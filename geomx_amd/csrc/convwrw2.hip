@@ -30,7 +30,9 @@
 // rows; 4 waves split the 25 (kh,kw) tap tiles round-robin and each
 // wave computes BOTH o-tiles for its taps (A-fragment reuse), keeping
 // all accumulators in VGPRs until one final per-workgroup slab flush
-// (partials summed in torch).
+// (partials summed in torch). The CI=4 kernel (conv1) packs its taps
+// differently and pipelines its reads and its staging; it is described
+// at k_conv5_wrw4_nhwc below.
 
 #include <hip/hip_runtime.h>
 
@@ -343,20 +345,82 @@ __global__ void k_tr16_probe(const bf16_t* __restrict__ in,
 // ---------------------------------------------------------------------
 // CI=4 variant (conv1: 4 padded channels -> 16 outputs).
 //
-// The CI=16 scheme needs 16-wide image rows so that a tr-read's j step
-// is ONE k-pixel on both operands. With 4 channels the natural image
-// rows are 4-wide, so instead we stage a KH-INTERLEAVED image
-//     I_p[pix][kho][ci] = in[row p+kho][pix][ci]   (kho = 0..3)
-// whose 16-wide rows make lane m = (kho*4+ci) the channel column and
-// keep the 1-pixel j step. Tap tiles become t = kw*2 + khg
-// (kw = 0..4, khg = 0..1, kh = khg*4+kho): 10 tiles of 16 slots hold
-// the 100 real taps (kh>4 slots are dead weight, 38%; their values are
-// whatever the clamped staging rows hold and are dropped at unpack).
-// Four interleaved images (p = r + 4*khg for r in 0..1, khg in 0..1)
-// are filled by 4-byte LDS-DMA granules (dest byte 4l maps to
-// pix = l>>3, kho = (l>>1)&3, ci-pair = l&1 — per-lane global source
-// does the interleave, dest stays lane-linear).
+// With 4 channels an image row is 8 B per pixel, so one tr-read quarter
+// (4 bf16) is one pixel's channels. The transpose read gathers PER-LANE
+// 8 B quarters (test_tr16_per_lane_gather: out[m][j] = mem[addr[4j +
+// (m>>2)] + (m&3) elems]), so a fragment's A row m = 4p + ci comes from
+// whatever (row, pixel) lane quarter p of the group points at, straight
+// from the raw [pix][4] input rows. The 100 taps and the bias sit in
+// SEVEN tiles (112 A rows, 101 live):
+//   T0..T4 (kw = T): quarter p -> row r+p, pixel kw + 4q + j
+//                    A row m = (kh = m>>2, ci = m&3)
+//   T5 (kh = 4):     quarter p -> row r+4, pixel p + 4q + j
+//                    A row m = (kw = m>>2, ci = m&3), kw = 0..3
+//   T6:              quarters 0, 2, 3 -> row r+4, pixel 4 + 4q + j
+//                    A rows 0..3 = (kh 4, kw 4, ci); quarter 1 points
+//                    into an LDS region of bf16 ones, so A row 4 is the
+//                    BIAS row (D[4][o] = sum_k B[k][o]) without a select
+//                    in the loop; rows 5..15 are dead
+// (j = (lane&15)>>2 is the k-pixel, p = lane&3; the read needs EXEC all
+// ones, so dead quarters get an in-bounds address and are dropped at the
+// flush). Row regions are skewed by 64 B so the 4 rows a T0..T4 group
+// touches land on distinct LDS banks; T5/T6 touch 11 consecutive pixels
+// of one row per 32-lane half. Waves own tiles {0,1} {2,3} {4,5} {6}:
+// 24 tr reads and 8 MFMAs per (row, window), one of each pair spare
+// (the 10-tile kernel: 32 and 11). One tile per wave on 8 waves measured
+// slower (docs/kernels.md).
+//
+// A D row depends on its own A row only, and every tile keeps the
+// k-slot -> pixel permutation and the (block, row, window) order of its
+// MFMAs, so each (tap, o) and bias sum is the sum the 10-tile kernel
+// (tiles t = kw*2 + kh/4, before) computed, bit for bit; the flush
+// scatters the live rows to that kernel's slab rows
+// (kw*2 + kh/4)*16 + (kh%4)*4 + ci, bias in row 160, and leaves the
+// other rows as the caller zeroed them.
+//
+// Schedule: fragment reads are compiler-counted builtins
+// (__builtin_amdgcn_ds_read_tr16_b64_v4i16), software-pipelined two
+// (row, window) steps ahead in three register sets, so a wave's reads
+// are in flight while its MFMAs run and no lgkmcnt(0) drain sits in the
+// walk (the builtin's result needs no repack ahead of a hand-placed
+// wait, which is what tied the 10-tile kernel to one asm block per
+// step). A full-width two-row block walks straight-line code whose
+// offsets are all immediates; other widths and one-row tails take a
+// loop with the same pipeline.
+// The A image is double-buffered: the next block's rows go by LDS-DMA
+// into the other image, and (UNPOOL) its pooled gradient and codes into
+// registers, right after the barrier that opens the MFMA phase; the
+// selects and ds_write_b128 that build the gout image run after the
+// barrier that ends it. The full-resolution form stages gout by LDS-DMA
+// into its single image between the two barriers.
 // ---------------------------------------------------------------------
+
+__device__ __forceinline__ bf16x4 tr16_ld(
+    const __attribute__((address_space(3))) char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) bf16x4*)p);
+}
+
+// One 1 KiB LDS-DMA piece (16 B per lane) that the compiler does not
+// see: for a __builtin_amdgcn_global_load_lds in flight hipcc puts
+// s_waitcnt vmcnt(0) ahead of the next LDS read it cannot prove
+// disjoint, which would end the prefetch of the NEXT block's image at
+// the first fragment read of this one. The kernel waits for its pieces
+// itself (vmcnt(0) ahead of the barrier that opens each MFMA phase).
+// `lds_dst` is the wave-uniform LDS byte address of the piece.
+__device__ __forceinline__ void glds16_unseen(const void* gsrc,
+                                              unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
+      : "memory");
+}
 
 template <int PIX, bool UNPOOL = false>
 __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
@@ -366,190 +430,274 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
     float* __restrict__ part,         // [nWG][176][16]
     int Nn, int Hi, int Wi, int Ho, int Wo,
     const uint8_t* __restrict__ mask) {  // UNPOOL: argmax codes, as gout
-  // v3: the transpose read gathers PER-LANE 8B quarters (verified by
-  // test_tr16_per_lane_gather: out[m][j] = mem[addr[4j+(m>>2)] +
-  // (m&3) elems]), so the A fragment (lane m = kho*4+ci) reads STRAIGHT
-  // from the 6 raw [pix][4] input rows: lane l points at
-  // row(r + khg*4 + (l&3)), pixel (pix0 + kw + 4q + (l>>2)&3).
-  // No kh-interleaved images, no 4x staging duplication: per block the
-  // A staging is 6 rows x PIX*8B once. Row regions are skewed by 64 B
-  // so the 4 rows a group touches land on distinct LDS banks.
   constexpr int CI = 4;
   constexpr int CO = 16;
-  constexpr int NT = 10;                  // (kw 0..4) x (khg 0..1)
-  constexpr int T16 = (NT + 1) * 16;      // +bias tile (wid 2, j 2)
+  constexpr int NT = 7;                   // packed tap tiles, bias in T6
+  constexpr int T16 = 176;                // slab rows (10 + 1 tiles)
   constexpr int AROW_BYTES = PIX * CI * 2;
   constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
   constexpr int ARPB = NCHA * 1024 + 64;  // 64B skew: distinct banks/row
   constexpr int BROW_BYTES = PIX * 16 * 2;
   constexpr int NCHB = (BROW_BYTES + 1023) / 1024;
   constexpr int BRPB = NCHB * 1024;
-  constexpr int NROW_A = 6;               // rows ho0 .. ho0+5
-  __shared__ __attribute__((aligned(128))) char lds_all[NROW_A * ARPB +
-                                                        WRW2_R * BRPB];
-  constexpr int BOFF = NROW_A * ARPB;
+  constexpr int NROW_A = WRW2_R + 4;      // rows ho0 .. ho0+5
+  constexpr int AIMG = NROW_A * ARPB;     // one A image; two of them
+  constexpr int BOFF = 2 * AIMG;
+  constexpr int WMAX = (PIX - 4) / 32;    // K windows of a full row
+  constexpr int ONES = BOFF + WRW2_R * BRPB;  // bf16 1.0, see ones_q
+  constexpr int ONES_BYTES = WRW2_THREADS * 16;
+  static_assert(AIMG % 128 == 0, "");
+  static_assert(ARPB + (WMAX - 1) * 256 + 128 + 8 <= ONES_BYTES,
+                "the bias quarter walks the same offsets as a pixel row");
+  __shared__ __attribute__((aligned(128))) char lds_all[ONES + ONES_BYTES];
 
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4;
   const int m = lane & 15;
-  const int wid = threadIdx.x >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   const int W = (Wo + 31) >> 5;
   const int blocks_h = (Ho + WRW2_R - 1) / WRW2_R;
   const long long n_blocks = (long long)Nn * blocks_h;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
+  const __attribute__((address_space(3))) char* lds3 =
+      (const __attribute__((address_space(3))) char*)lds_all;
   const unsigned lds0 = lds_addr(lds_all);
 
-  constexpr int MAXT = 3;
-  f32x4 acc[MAXT];
+  // wave-owned tiles t = 2*wid + j. The spare slot (wid 3, j 1) repeats
+  // T6 into an accumulator that is never flushed: the walk then has no
+  // wave-dependent branch, so the compiler can count its lgkmcnt waits.
+  constexpr int TPW = 2;
+  f32x4 acc[TPW];
+  // per-lane fragment bases at (r 0, window 0) of A image 0
+  const __attribute__((address_space(3))) char* abase[TPW];
 #pragma unroll
-  for (int j = 0; j < MAXT; ++j) acc[j] = (f32x4)0.0f;
+  for (int j = 0; j < TPW; ++j) {
+    acc[j] = (f32x4)0.0f;
+    const int t = (2 * wid + j) < NT ? 2 * wid + j : NT - 1;
+    const int p = lane & 3;
+    const int kpix = 4 * q + (m >> 2);
+    const int row = t < 5 ? p : 4;
+    const int pix = (t < 5 ? t : (t == 5 ? p : 4)) + kpix;
+    abase[j] = lds3 + row * ARPB + pix * 8;
+  }
+  // T6's quarter 1 (A rows 4..7; row 4 is the bias row) reads constant
+  // bf16 ones instead of pixels: its lanes walk the ONES region, filled
+  // once here and made visible by the first block's barrier, with the
+  // offsets the other quarters walk a pixel row with. Rows 5..7 are dead.
+  const bool ones_q = (wid == 3) && ((lane & 3) == 1);
+  const __attribute__((address_space(3))) char* ones_p = lds3 + ONES;
+  reinterpret_cast<uint4*>(lds_all + ONES)[threadIdx.x] =
+      make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
+  const __attribute__((address_space(3))) char* bbase =
+      lds3 + BOFF + (4 * q) * 32 + m * 8;
 
-  for (long long blk = wg; blk < n_blocks; blk += n_wg) {
-    const int bh = (int)(blk % blocks_h);
-    const long long n = blk / blocks_h;
+  // ---- staging pieces. A rows by LDS-DMA (16 B = 2 pixels per lane),
+  // chunks round-robin over the 4 waves; only the nrows + 4 rows the
+  // block's taps read are fetched.
+  auto stage_a = [&](long long n, int bh, int img) {
+    const int ho0 = bh * WRW2_R;
+    const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
+    const int nchunks_a = (nrows + 4) * NCHA;
+    for (int t = wid; t < nchunks_a; t += 4) {
+      const int ir = t / NCHA;
+      const int c = t - ir * NCHA;
+      const int slot = c * 64 + lane;              // 16B = 2 pixels
+      const int pix = slot * 2;
+      const bf16_t* src =
+          (pix + 1 < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
+                                 (long long)pix * CI)
+                         : g_wrw2_zeros;
+      glds16_unseen(src, lds0 + img * AIMG + ir * ARPB + c * 1024);
+    }
+  };
+  // UNPOOL: both gout rows of a block come from pooled row bh and its
+  // argmax codes (Ho, Wo even). Item `it` = threadIdx.x is one 16 B
+  // granule (8 channels) of pooled pixel it>>1 and expands to its 4
+  // full-resolution positions; items past the row write the zero tail
+  // [Wo, 32*W) the K windows read. At most one item per thread:
+  // 16 * 7 windows * 2 granules = 224.
+  static_assert(16 * ((PIX - 4) / 32) * 2 <= WRW2_THREADS, "");
+  uint4 gq = make_uint4(0u, 0u, 0u, 0u);
+  uint2 mq = make_uint2(~0u, ~0u);
+  auto load_pooled = [&](long long n, int bh) {
+    const long long rowv = (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * 2;
+    if ((int)threadIdx.x < (Wo >> 1) * 2) {
+      gq = reinterpret_cast<const uint4*>(gout)[rowv + threadIdx.x];
+      mq = reinterpret_cast<const uint2*>(mask)[rowv + threadIdx.x];
+    }
+  };
+  auto write_pooled = [&]() {
+    const int it = threadIdx.x;
+    if (it < 16 * W * 2) {
+      const int wp = it >> 1;
+      const int half = it & 1;
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx)
+          *reinterpret_cast<uint4*>(lds_all + BOFF + dy * BRPB +
+                                    (2 * wp + dx) * 32 + half * 16) =
+              unpool_select(gq, mq, dy * 2 + dx);
+    }
+  };
+  auto stage_b = [&](long long n, int bh) {
+    const int ho0 = bh * WRW2_R;
+    const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
+    const int nchunks_b = nrows * NCHB;
+    for (int t = wid; t < nchunks_b; t += 4) {
+      const int rr = t / NCHB;
+      const int c = t - rr * NCHB;
+      const int slot = c * 64 + lane;
+      const int pix = slot >> 1;
+      const bf16_t* src =
+          (pix < Wo) ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
+                               (long long)slot * 8)
+                     : g_wrw2_zeros;
+      glds16_unseen(src, lds0 + BOFF + rr * BRPB + c * 1024);
+    }
+  };
+
+  // one (row, window) step's fragments: B lo/hi and per tile A lo/hi
+  // (hi = k-pixels 16..31: +512 B in the gout image, +128 B in a row)
+  struct Frag {
+    bf16x4 b[2];
+    bf16x4 a[TPW][2];
+  };
+
+  // block = (image n, row pair bh), decoded once, one block ahead
+  long long blk = wg;
+  int img = 0;
+  long long n = 0;
+  int bh = 0;
+  if (blk < n_blocks) {
+    n = blk / blocks_h;
+    bh = (int)(blk - n * blocks_h);
+    stage_a(n, bh, 0);
+    if constexpr (UNPOOL) load_pooled(n, bh);
+  }
+  for (; blk < n_blocks; blk += n_wg, img ^= 1) {
     const int ho0 = bh * WRW2_R;
     const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
 
-    // ---- stage 6 raw input rows + gout rows (16B LDS-DMA granules)
-    {
-      const int nchunks_a = NROW_A * NCHA;
-      for (int t = wid; t < nchunks_a; t += 4) {
-        const int ir = t / NCHA;
-        const int c = t - ir * NCHA;
-        const int slot = c * 64 + lane;              // 16B = 2 pixels
-        const int pix = slot * 2;
-        int row = ho0 + ir;
-        if (row >= Hi) row = Hi - 1;                 // tail blocks only
-        const bf16_t* src =
-            (pix + 1 < Wi) ? in + ((n * Hi + row) * (long long)Wi * CI +
-                                   (long long)pix * CI)
-                           : g_wrw2_zeros;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)src,
-            (__attribute__((address_space(3))) void*)(lds_all + ir * ARPB +
-                                                      c * 1024),
-            16, 0, 0);
-      }
-      if constexpr (UNPOOL) {
-        // both gout rows from pooled row bh + its argmax mask, exactly
-        // as in k_conv5_wrw16_nhwc (one o-tile; at most one item per
-        // thread: 16 * 7 windows * 2 granules = 224)
-        static_assert(16 * ((PIX - 4) / 32) * 2 <= WRW2_THREADS, "");
-        const int it = threadIdx.x;
-        const int nit = 16 * W * 2;
-        const int nreal = (Wo >> 1) * 2;
-        const long long rowv =
-            (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * 2;
-        uint4 gq = make_uint4(0u, 0u, 0u, 0u);
-        uint2 mq = make_uint2(~0u, ~0u);
-        if (it < nreal) {
-          gq = reinterpret_cast<const uint4*>(gout)[rowv + it];
-          mq = reinterpret_cast<const uint2*>(mask)[rowv + it];
-        }
-        if (it < nit) {
-          const int wp = it >> 1;
-          const int half = it & 1;
-#pragma unroll
-          for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx)
-              *reinterpret_cast<uint4*>(lds_all + BOFF + dy * BRPB +
-                                        (2 * wp + dx) * 32 + half * 16) =
-                  unpool_select(gq, mq, dy * 2 + dx);
-        }
-      }
-      const int nchunks_b = UNPOOL ? 0 : nrows * NCHB;
-      for (int t = wid; t < nchunks_b; t += 4) {
-        const int rr = t / NCHB;
-        const int c = t - rr * NCHB;
-        const int slot = c * 64 + lane;
-        const int pix = slot >> 1;
-        const bf16_t* src =
-            (pix < Wo) ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
-                                 (long long)slot * 8)
-                       : g_wrw2_zeros;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)src,
-            (__attribute__((address_space(3))) void*)(lds_all + BOFF +
-                                                      rr * BRPB + c * 1024),
-            16, 0, 0);
-      }
+    // ---- the gout image of this block (the A image was prefetched)
+    if constexpr (UNPOOL) {
+      write_pooled();
+    } else {
+      stage_b(n, bh);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // vmcnt(0), as a builtin so that the compiler's own bookkeeping of
+    // the pooled loads sees it (an asm wait would leave it re-waiting,
+    // on the DMA pieces just issued, before the next load_pooled)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
 
-    for (int r = 0; r < nrows; ++r) {
-      // per-lane A bases: lane quarter l&15 supplies
-      // row(r + khg*4 + (lane&3)), pixel (kw + 4q + ((lane&15)>>2))
-      unsigned abase[MAXT];
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        int t = wid + 4 * j;
-        if (t >= NT) t = NT - 1;
-        const int kw = t >> 1;
-        const int khg = t & 1;
-        int rowsel = r + khg * 4 + (lane & 3);
-        if (rowsel > NROW_A - 1) rowsel = NROW_A - 1;  // dead taps only
-        abase[j] = lds0 + rowsel * ARPB +
-                   (unsigned)((kw + 4 * q + ((lane & 15) >> 2)) * 8);
-      }
-      const unsigned bbase = lds0 + BOFF + r * BRPB + (4 * q) * 32 + m * 8;
-      for (int w = 0; w < W; ++w) {
-        const unsigned poffB = (unsigned)(w * 32 * 32);
-        const unsigned poffA = (unsigned)(w * 32 * 8);
-        bf16x4 fr[8];
-        asm volatile(
-            "ds_read_b64_tr_b16 %0, %8\n\t"
-            "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-            "ds_read_b64_tr_b16 %2, %9\n\t"
-            "ds_read_b64_tr_b16 %3, %9 offset:128\n\t"
-            "ds_read_b64_tr_b16 %4, %10\n\t"
-            "ds_read_b64_tr_b16 %5, %10 offset:128\n\t"
-            "ds_read_b64_tr_b16 %6, %11\n\t"
-            "ds_read_b64_tr_b16 %7, %11 offset:128\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(fr[0]), "=&v"(fr[1]), "=&v"(fr[2]), "=&v"(fr[3]),
-              "=&v"(fr[4]), "=&v"(fr[5]), "=&v"(fr[6]), "=&v"(fr[7])
-            : "v"(bbase + poffB), "v"(abase[0] + poffA),
-              "v"(abase[1] + poffA), "v"(abase[2] + poffA)
-            : "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
-        b.p.lo = fr[0];
-        b.p.hi = fr[1];
-#pragma unroll
-        for (int j = 0; j < MAXT; ++j) {
-          const int t = wid + 4 * j;
-          const bool bias_tile = (t == NT);  // spare slot: wid 2, j 2
-          if (t >= NT && !bias_tile) continue;
-          union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
-          if (bias_tile) {
-            const bf16x8 ones = (bf16x8)(short)0x3F80;
-            a.v = (m == 0) ? ones : (bf16x8)(short)0;
-          } else {
-            a.p.lo = fr[2 + 2 * j];
-            a.p.hi = fr[3 + 2 * j];
-          }
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v,
-                                                           acc[j], 0, 0, 0);
-        }
-      }
+    // ---- the next block's fetches fly during this block's MFMA phase
+    if (blk + n_wg < n_blocks) {
+      n = (blk + n_wg) / blocks_h;
+      bh = (int)(blk + n_wg - n * blocks_h);
+      stage_a(n, bh, img ^ 1);
+      if constexpr (UNPOOL) load_pooled(n, bh);
     }
-    __syncthreads();
+
+    // ---- walk the (row, window) steps s = r*W + w in order, fragment
+    // reads two steps ahead of their MFMAs in three register sets.
+    // Step (r, w) is a constant offset from the block's per-lane bases.
+    const __attribute__((address_space(3))) char* ab0 =
+        ones_q ? ones_p : abase[0] + img * AIMG;   // T6 is (wid 3, j 0)
+    const __attribute__((address_space(3))) char* ab1 =
+        abase[1] + img * AIMG;
+    auto load = [&](Frag& f, int r, int w) {
+      const int oa = r * ARPB + w * (32 * 8);
+      const int ob = r * BRPB + w * (32 * 32);
+      f.b[0] = tr16_ld(bbase + ob);
+      f.b[1] = tr16_ld(bbase + ob + 512);
+      f.a[0][0] = tr16_ld(ab0 + oa);
+      f.a[0][1] = tr16_ld(ab0 + oa + 128);
+      f.a[1][0] = tr16_ld(ab1 + oa);
+      f.a[1][1] = tr16_ld(ab1 + oa + 128);
+    };
+    auto mma = [&](const Frag& f) {
+      union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
+      b.p.lo = f.b[0];
+      b.p.hi = f.b[1];
+#pragma unroll
+      for (int j = 0; j < TPW; ++j) {
+        union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
+        a.p.lo = f.a[j][0];
+        a.p.hi = f.a[j][1];
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc[j],
+                                                         0, 0, 0);
+      }
+    };
+    // The sched_barriers keep each step's reads ahead of the MFMAs they
+    // overlap; the compiler places the counted lgkmcnt waits.
+    Frag f[3];
+    if (W == WMAX && nrows == WRW2_R) {
+      // full-width two-row block (the flagship): every offset is an
+      // immediate, the walk is straight-line code
+      constexpr int NS = WRW2_R * WMAX;
+      load(f[0], 0, 0);
+      load(f[1], 1 / WMAX, 1 % WMAX);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (s + 2 < NS) load(f[(s + 2) % 3], (s + 2) / WMAX, (s + 2) % WMAX);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(f[s % 3]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      // any other width, and one-row tail blocks. A step past the last
+      // re-reads the last one (in bounds, unused); no branch in a trip.
+      const int nsteps = nrows * W;
+      static_assert(WRW2_R == 2, "ld() decodes r from one compare");
+      auto ld = [&](Frag& fr, int s) {
+        if (s > nsteps - 1) s = nsteps - 1;
+        const int r = s >= W ? 1 : 0;
+        load(fr, r, s - (r ? W : 0));
+      };
+      ld(f[0], 0);
+      ld(f[1], 1);
+      int s = 0;
+      for (; s + 2 < nsteps; s += 3) {
+        ld(f[2], s + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(f[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(f[0], s + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(f[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(f[1], s + 4);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(f[2]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // the last nsteps % 3 steps; their reads are already in flight
+      if (s < nsteps) mma(f[0]);
+      if (s + 1 < nsteps) mma(f[1]);
+    }
+    __syncthreads();  // before the next block rebuilds the gout image
   }
 
-  // ---- flush: part[wg][t*16 + m][o], D row = q*4+i = slot m, col = o
+  // ---- flush the live D rows (row = q*4 + i, col = m = o) to the slab
+  // rows of the 10-tile layout; everything else stays as zeroed
   float* base = part + (long long)wg * T16 * CO;
 #pragma unroll
-  for (int j = 0; j < MAXT; ++j) {
-    const int t = wid + 4 * j;
-    if (t > NT) continue;                // NT itself = the bias tile
+  for (int j = 0; j < TPW; ++j) {
+    const int t = 2 * wid + j;
+    if (t >= NT) continue;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int slot = t * 16 + q * 4 + i;
-      base[(long long)slot * CO + m] = acc[j][i];
+      int slot;
+      if (t < 5)                          // kw = t, kh = q, ci = i
+        slot = t * 32 + q * 4 + i;
+      else if (t == 5)                    // kh = 4, kw = q, ci = i
+        slot = (q * 2 + 1) * 16 + i;
+      else                                // kh 4, kw 4 | bias | dead
+        slot = q == 0 ? 9 * 16 + i : ((q == 1 && i == 0) ? 160 : -1);
+      if (slot >= 0) base[(long long)slot * CO + m] = acc[j][i];
     }
   }
 }
