@@ -55,6 +55,24 @@ void geops_signsgd_update(float*, const float*, float, float, float,
                           long long, hipStream_t);
 void geops_signum_update(float*, const float*, float*, float, float, float,
                          float, long long, hipStream_t);
+// rowsparse.hip
+void geops_rsp_merge(const long long*, const long long*, const long long*,
+                     const float*, long long*, float*, long long, long long,
+                     hipStream_t);
+void geops_rsp_scatter(const long long*, const float*, float*, long long,
+                       long long, long long, bool, hipStream_t);
+void geops_rsp_sgd_update(const long long*, const float*, float*, float,
+                          float, float, long long, long long, long long,
+                          hipStream_t);
+void geops_rsp_sgd_mom_update(const long long*, const float*, float*, float*,
+                              float, float, float, float, long long,
+                              long long, long long, hipStream_t);
+void geops_rsp_adam_update(const long long*, const float*, float*, float*,
+                           float*, float, float, float, float, float, float,
+                           long long, long long, long long, hipStream_t);
+void geops_rsp_adagrad_update(const long long*, const float*, float*, float*,
+                              float, float, float, float, long long,
+                              long long, long long, hipStream_t);
 void geops_relu_maxpool2_fwd(const unsigned short*, unsigned short*, uint8_t*,
                              long long, int, int, int, hipStream_t);
 void geops_relu_maxpool2_bwd(const unsigned short*, const uint8_t*,
@@ -635,6 +653,126 @@ void signum_update(torch::Tensor w, torch::Tensor g, torch::Tensor mom,
   launch_check("signum_update");
 }
 
+// -- row-sparse push (rowsparse.hip) ---------------------------------------
+// No 16-byte demand here: stored values and optimizer state may be views
+// at odd element offsets; the launchers pick the scalar instantiation.
+void check_rsp_f32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
+}
+
+void check_rsp_i64(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.is_contiguous() && t.dim() == 1, name,
+              " must be contiguous 1-d");
+  TORCH_CHECK(t.scalar_type() == torch::kInt64, name, " must be int64");
+}
+
+const long long* i64p(const torch::Tensor& t) {
+  return (const long long*)t.data_ptr<int64_t>();
+}
+
+// shared shape contract of scatter / row updates: table [rows][width],
+// merged [n_u][width], ids [n_u]
+void check_rsp_rows(const torch::Tensor& table, const torch::Tensor& ids,
+                    const torch::Tensor& merged) {
+  check_rsp_f32(table, "table"); check_rsp_f32(merged, "merged");
+  check_rsp_i64(ids, "ids");
+  TORCH_CHECK(table.dim() == 2 && merged.dim() == 2,
+              "table and merged must be 2-d");
+  TORCH_CHECK(merged.size(0) == ids.numel() &&
+              merged.size(1) == table.size(1),
+              "merged must be [len(ids)][width]");
+}
+
+void check_rsp_state(const torch::Tensor& s, const torch::Tensor& table,
+                     const char* name) {
+  check_rsp_f32(s, name);
+  TORCH_CHECK(s.sizes() == table.sizes(), name, " must match the table");
+}
+
+void rsp_merge(torch::Tensor sorted_ids, torch::Tensor perm,
+               torch::Tensor seg, torch::Tensor vals, torch::Tensor out_ids,
+               torch::Tensor out_vals) {
+  check_rsp_i64(sorted_ids, "sorted_ids"); check_rsp_i64(perm, "perm");
+  check_rsp_i64(seg, "seg"); check_rsp_i64(out_ids, "out_ids");
+  check_rsp_f32(vals, "vals"); check_rsp_f32(out_vals, "out_vals");
+  const long long nnz = sorted_ids.numel();
+  TORCH_CHECK(perm.numel() == nnz && seg.numel() == nnz &&
+              out_ids.numel() == nnz, "id arrays must all hold nnz entries");
+  TORCH_CHECK(vals.dim() == 2 && vals.size(0) == nnz &&
+              out_vals.sizes() == vals.sizes(),
+              "vals and out_vals must be [nnz][width]");
+  geops_rsp_merge(i64p(sorted_ids), i64p(perm), i64p(seg),
+                  vals.data_ptr<float>(),
+                  (long long*)out_ids.data_ptr<int64_t>(),
+                  out_vals.data_ptr<float>(), nnz, vals.size(1),
+                  cur_stream());
+  launch_check("rsp_merge");
+}
+
+void rsp_scatter(torch::Tensor dense, torch::Tensor ids,
+                 torch::Tensor merged, bool accumulate) {
+  check_rsp_rows(dense, ids, merged);
+  geops_rsp_scatter(i64p(ids), merged.data_ptr<float>(),
+                    dense.data_ptr<float>(), ids.numel(), dense.size(0),
+                    dense.size(1), accumulate, cur_stream());
+  launch_check("rsp_scatter");
+}
+
+void rsp_sgd_update(torch::Tensor w, torch::Tensor ids, torch::Tensor merged,
+                    double lr, double wd, double rescale) {
+  check_rsp_rows(w, ids, merged);
+  geops_rsp_sgd_update(i64p(ids), merged.data_ptr<float>(),
+                       w.data_ptr<float>(), (float)lr, (float)wd,
+                       (float)rescale, ids.numel(), w.size(0), w.size(1),
+                       cur_stream());
+  launch_check("rsp_sgd_update");
+}
+
+void rsp_sgd_mom_update(torch::Tensor w, torch::Tensor ids,
+                        torch::Tensor merged, torch::Tensor mom, double lr,
+                        double momentum, double wd, double rescale) {
+  check_rsp_rows(w, ids, merged);
+  check_rsp_state(mom, w, "mom");
+  geops_rsp_sgd_mom_update(i64p(ids), merged.data_ptr<float>(),
+                           w.data_ptr<float>(), mom.data_ptr<float>(),
+                           (float)lr, (float)momentum, (float)wd,
+                           (float)rescale, ids.numel(), w.size(0), w.size(1),
+                           cur_stream());
+  launch_check("rsp_sgd_mom_update");
+}
+
+void rsp_adam_update(torch::Tensor w, torch::Tensor ids, torch::Tensor merged,
+                     torch::Tensor m, torch::Tensor v, int64_t t, double lr,
+                     double beta1, double beta2, double eps, double wd,
+                     double rescale) {
+  check_rsp_rows(w, ids, merged);
+  check_rsp_state(m, w, "m"); check_rsp_state(v, w, "v");
+  const double lr_t =
+      lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) /
+      (1.0 - std::pow(beta1, (double)t));
+  geops_rsp_adam_update(i64p(ids), merged.data_ptr<float>(),
+                        w.data_ptr<float>(), m.data_ptr<float>(),
+                        v.data_ptr<float>(), (float)lr_t, (float)beta1,
+                        (float)beta2, (float)eps, (float)wd, (float)rescale,
+                        ids.numel(), w.size(0), w.size(1), cur_stream());
+  launch_check("rsp_adam_update");
+}
+
+void rsp_adagrad_update(torch::Tensor w, torch::Tensor ids,
+                        torch::Tensor merged, torch::Tensor h, double lr,
+                        double eps, double wd, double rescale) {
+  check_rsp_rows(w, ids, merged);
+  check_rsp_state(h, w, "h");
+  geops_rsp_adagrad_update(i64p(ids), merged.data_ptr<float>(),
+                           w.data_ptr<float>(), h.data_ptr<float>(),
+                           (float)lr, (float)eps, (float)wd, (float)rescale,
+                           ids.numel(), w.size(0), w.size(1), cur_stream());
+  launch_check("rsp_adagrad_update");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -688,4 +826,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adagrad_update", &adagrad_update);
   m.def("signsgd_update", &signsgd_update);
   m.def("signum_update", &signum_update);
+  m.def("rsp_merge", &rsp_merge);
+  m.def("rsp_scatter", &rsp_scatter);
+  m.def("rsp_sgd_update", &rsp_sgd_update);
+  m.def("rsp_sgd_mom_update", &rsp_sgd_mom_update);
+  m.def("rsp_adam_update", &rsp_adam_update);
+  m.def("rsp_adagrad_update", &rsp_adagrad_update);
 }

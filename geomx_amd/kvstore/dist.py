@@ -424,6 +424,16 @@ class KVStoreDist(KVStoreBase):
             for v in value[1:]:
                 acc += v.detach().reshape(-1).float().to(acc.device)
             value = acc
+        if value.layout == torch.sparse_coo:
+            # nn.Embedding(sparse=True) gradients: row-sparse by
+            # construction. _indices/_values read the uncoalesced tensor;
+            # the row-sparse merge sums the duplicates itself.
+            if value.sparse_dim() != 1:
+                raise ValueError("push of a sparse value needs "
+                                 "sparse_dim == 1 (row-sparse)")
+            self.push_row_sparse(key, value._indices()[0], value._values(),
+                                 priority)
+            return
         st = self._state(key)
         if value.numel() != st.numel:
             raise ValueError(f"push size mismatch for {key!r}")
@@ -461,6 +471,9 @@ class KVStoreDist(KVStoreBase):
         self._pending_map = {}
         for _prio, _seq, key, pend in entries:
             st = self.keys[key]
+            if pend[0] == "rsp":
+                self._rsp_post(key, st, pend[1])
+                continue
             party_sum = self._party_finish(st, pend)
             self._post_aggregate(key, st, party_sum)
 
@@ -835,20 +848,210 @@ class KVStoreDist(KVStoreBase):
                         values: torch.Tensor, priority: int = 0) -> None:
         """Push a row-sparse gradient (rows named by row_ids, one value
         row each — the reference's row_sparse push storage,
-        kvstore_dist.h:900 EncodeRowSparseKey). Duplicate ids
-        accumulate. Densified before the wire: in-node xGMI bandwidth
-        makes dense collectives the faster transport for these sizes."""
+        kvstore_dist.h:628 PushRowSparse / :900 EncodeRowSparseKey).
+        Duplicate ids accumulate.
+
+        Rows-only route (plain dense-fp32 keys, see _rsp_rows_route):
+        every tier ships only the present rows — workers pre-merge their
+        duplicates and send (ids, rows) to the party leader, leaders
+        exchange their merged lists, and the server applies one
+        row-indexed update (ServerOptimizer.update_rows; lazy when the
+        spec asks for it). Sums are deterministic: duplicates add in
+        ascending position, senders in rank order. The party tier runs
+        here; the WAN tier and the update are deferred to flush() in
+        (priority, seq) order like push().
+
+        Compressed wires, HFA, the store transport, TSEngine, sliced
+        keys and custom updaters densify and take push() as before.
+
+        CPU ids are range-checked here; GPU ids are not (the check would
+        synchronize) — the kernels skip ids outside [0, rows)."""
         st = self._state(key)
         if len(st.shape) < 2:
             raise ValueError("push_row_sparse needs a >=2d key")
         rows = st.shape[0]
         width = st.numel // rows
-        dense = torch.zeros(rows, width, dtype=torch.float32,
-                            device=self._device)
-        dense.index_add_(0, row_ids.to(self._device).long(),
-                         values.detach().reshape(-1, width).float()
-                         .to(self._device))
-        self.push(key, dense, priority)
+        ids = row_ids.reshape(-1)
+        if not ids.is_cuda and ids.numel() > 0 and (
+                int(ids.min()) < 0 or int(ids.max()) >= rows):
+            raise ValueError(
+                f"push_row_sparse: row ids out of range [0, {rows}) "
+                f"for key {key!r}")
+        if not self._rsp_rows_route(st):
+            dense = torch.zeros(rows, width, dtype=torch.float32,
+                                device=self._device)
+            dense.index_add_(0, row_ids.to(self._device).long(),
+                             values.detach().reshape(-1, width).float()
+                             .to(self._device))
+            self.push(key, dense, priority)
+            return
+        vals = values.detach().reshape(-1, width).float().to(self._device)
+        ids = ids.long().to(self._device)
+        if vals.shape[0] != ids.numel():
+            raise ValueError(f"push_row_sparse: {ids.numel()} ids but "
+                             f"{vals.shape[0]} value rows for {key!r}")
+        if key in self._pending:
+            self.flush()
+        st.push_count += 1
+        mine = ops.rsp_merge(ids, vals)  # worker pre-merge
+        party = self._rsp_party_tier(mine, width)
+        self._pending[key] = (priority, self._push_seq, key,
+                              ("rsp", party, None, None))
+        self._push_seq += 1
+
+    # -- row-sparse push: rows-only tiers ---------------------------------
+    def _rsp_rows_route(self, st: _KeyState) -> bool:
+        """True when push_row_sparse may ship rows only. Decided from
+        config and key state alone, which are identical on every rank,
+        so all ranks agree (self._ts is NOT: only leaders hold one)."""
+        cfg = self.cfg
+        ts_on = (cfg.enable_ts and self.global_mode == "replicated"
+                 and self.topo.num_parties > 1 and cfg.mode == "dist_sync")
+        return (cfg.mode in ("dist_sync", "dist_async")
+                and not cfg.use_hfa and not self._use_aps() and not ts_on
+                and self._effective_ctype(st) is None and not st.sliced
+                and not isinstance(self.optimizer, _UpdaterAdapter))
+
+    @staticmethod
+    def _rsp_compact(ids: torch.Tensor, rows: torch.Tensor, dev):
+        """Drop the -1 padded slots of a merge result and move it to
+        `dev` for the wire. Reads the count to the host — used only where
+        the wire needs one anyway."""
+        keep = ids >= 0
+        return ids[keep].to(dev), rows[keep].to(dev).contiguous()
+
+    def _rsp_party_tier(self, mine, width: int):
+        """Workers -> party leader, rows only. Returns the party's merged
+        (ids, rows) on the leader (own list first, then peers in party-
+        rank order), None elsewhere."""
+        topo = self.topo
+        if topo.world_size == 1 or topo.num_workers == 1:
+            return mine
+        cdev = self._comm_device()
+        my_ids, my_rows = self._rsp_compact(mine[0], mine[1], cdev)
+        counts = [torch.zeros(1, dtype=torch.int64, device=cdev)
+                  for _ in range(topo.num_workers)]
+        comm.all_gather(counts, torch.tensor([my_ids.numel()],
+                                             dtype=torch.int64, device=cdev),
+                        group=topo.party_group)
+        if not topo.is_leader:
+            if my_ids.numel() > 0:
+                comm.send(my_ids, dst=topo.leader_rank)
+                comm.send(my_rows, dst=topo.leader_rank)
+            return None
+        id_l, row_l = [my_ids], [my_rows]
+        for i, r in enumerate(topo.party_ranks):
+            n = int(counts[i].item())
+            if r == topo.rank or n == 0:
+                continue
+            ibuf = torch.empty(n, dtype=torch.int64, device=cdev)
+            rbuf = torch.empty(n, width, device=cdev)
+            comm.recv(ibuf, src=r)
+            comm.recv(rbuf, src=r)
+            id_l.append(ibuf)
+            row_l.append(rbuf)
+        return ops.rsp_merge(torch.cat(id_l).to(self._device),
+                             torch.cat(row_l).to(self._device))
+
+    def _rsp_global_exchange(self, st: _KeyState, party, width: int):
+        """Leader-tier rows-only exchange. Returns the per-party
+        (ids, rows) contributions in party order on ranks that apply the
+        update (every leader in replicated/async, the owner in sharded
+        sync), else None."""
+        topo = self.topo
+        P = topo.num_parties
+        group = topo.leader_group
+        cdev = self._comm_device()
+        ids, rows = self._rsp_compact(party[0], party[1], cdev)
+        n = ids.numel()
+        if self.global_mode == "replicated" or self.cfg.mode == "dist_async":
+            counts = [torch.zeros(1, dtype=torch.int64, device=cdev)
+                      for _ in range(P)]
+            comm.all_gather(counts, torch.tensor([n], dtype=torch.int64,
+                                                 device=cdev), group=group)
+            self.wan.charge(cross_party_bytes("all_gather", 8, P))
+            cnts = [int(c.item()) for c in counts]
+            max_cnt = max(cnts)
+            if max_cnt == 0:
+                # nothing to ship anywhere: every rank skips both payload
+                # collectives (the counts are identical on all of them)
+                empty = (ids, rows.reshape(0, width))
+                return [empty] * P
+            pid = torch.full((max_cnt,), -1, dtype=torch.int64, device=cdev)
+            prow = torch.zeros(max_cnt, width, device=cdev)
+            pid[:n] = ids
+            prow[:n] = rows
+            idl = [torch.empty_like(pid) for _ in range(P)]
+            rowl = [torch.empty_like(prow) for _ in range(P)]
+            comm.all_gather(idl, pid, group=group)
+            comm.all_gather(rowl, prow, group=group)
+            self.wan.charge(cross_party_bytes(
+                "all_gather", max_cnt * (width * 4 + 8), P))
+            return [(idl[p][:cnts[p]], rowl[p][:cnts[p]]) for p in range(P)]
+        # sharded sync: non-owner leaders ship (count, ids, rows) to the
+        # owner (the push mirror of _global_pull_rows)
+        owner_leader = topo.leader_ranks[st.owner_party]
+        if topo.rank != owner_leader:
+            comm.send(torch.tensor([n], dtype=torch.int64, device=cdev),
+                      dst=owner_leader)
+            if n > 0:
+                comm.send(ids, dst=owner_leader)
+                comm.send(rows, dst=owner_leader)
+                self.wan.charge(rows.numel() * 4 + ids.numel() * 8)
+            return None
+        contribs = []
+        for r in topo.leader_ranks:
+            if r == owner_leader:
+                contribs.append((ids, rows))
+                continue
+            cnt = torch.zeros(1, dtype=torch.int64, device=cdev)
+            comm.recv(cnt, src=r)
+            m = int(cnt.item())
+            ibuf = torch.empty(m, dtype=torch.int64, device=cdev)
+            rbuf = torch.empty(m, width, device=cdev)
+            if m > 0:
+                comm.recv(ibuf, src=r)
+                comm.recv(rbuf, src=r)
+                self.wan.charge(rbuf.numel() * 4 + ibuf.numel() * 8)
+            contribs.append((ibuf, rbuf))
+        return contribs
+
+    def _rsp_post(self, key, st: _KeyState, party) -> None:
+        """Deferred half of a rows-only push: WAN tier + server update
+        (the row-sparse _post_aggregate)."""
+        topo = self.topo
+        if not topo.is_leader:
+            return
+        rows = st.shape[0]
+        width = st.numel // rows
+        if topo.num_parties == 1:
+            contribs = [party]
+        else:
+            contribs = self._rsp_global_exchange(st, party, width)
+            if contribs is None:
+                return
+            contribs = [(i.to(self._device), r.to(self._device))
+                        for i, r in contribs]
+        w2d = st.stored.reshape(rows, width)
+        if self.cfg.mode == "dist_async" and self.optimizer is not None \
+                and len(contribs) > 1:
+            # async global tier: one sequential step per party's push
+            for i, r in contribs:
+                self.optimizer.update_rows(key, w2d, i, r)
+            return
+        if len(contribs) == 1:
+            ids, merged = contribs[0]
+        else:
+            ids, merged = ops.rsp_merge(torch.cat([c[0] for c in contribs]),
+                                        torch.cat([c[1] for c in contribs]))
+        if self.optimizer is not None:
+            self.optimizer.update_rows(key, w2d, ids, merged)
+        else:
+            # update-on-worker mode: stored holds the aggregated gradient
+            dense = torch.zeros(rows, width, dtype=torch.float32,
+                                device=self._device)
+            ops.rsp_scatter(dense, ids, merged)
+            st.stored = dense.reshape(-1)
 
     def _comm_device(self) -> torch.device:
         return torch.device("cpu") if self.topo.backend == "gloo" \

@@ -36,6 +36,10 @@ class OptimizerSpec:
                                            # rescale (optimizer.py:912 —
                                            # every reference optimizer
                                            # clips this way)
+    lazy_update: bool = False    # row-sparse pushes leave the weight AND
+                                 # the state of absent rows untouched
+                                 # (MXNet lazy_update; its default is True,
+                                 # ours False keeps dense-equivalent results)
 
     def validate(self):
         if self.name not in ("sgd", "sgd_mom", "adam", "dcasgd", "rmsprop",
@@ -61,6 +65,8 @@ class ServerOptimizer:
         self.spec = spec.validate()
         self.state: Dict[object, Dict[str, torch.Tensor]] = {}
         self.step_count: Dict[object, int] = {}
+        # per-key zeroed dense gradient for update_rows' dense fallback
+        self._dense_grad: Dict[object, torch.Tensor] = {}
 
     def _get_state(self, key, w: torch.Tensor) -> Dict[str, torch.Tensor]:
         st = self.state.get(key)
@@ -115,6 +121,59 @@ class ServerOptimizer:
             ops.signsgd_update(w, grad, s.lr, s.wd, rs)
         elif s.name == "signum":
             ops.signum_update(w, grad, st["mom"], s.lr, s.momentum, s.wd, rs)
+
+    _ROW_KERNELS = ("sgd", "sgd_mom", "adam", "adagrad")
+
+    def update_rows(self, key, w2d: torch.Tensor, ids: torch.Tensor,
+                    rows: torch.Tensor, rescale: Optional[float] = None):
+        """Apply one update from a merged row-sparse gradient: `rows[u]`
+        is the gradient of row `ids[u]` of `w2d` ([table rows][width]
+        fp32); ids are unique, out-of-range ids (-1 padding) are skipped.
+
+        With spec.lazy_update the sgd / sgd_mom / adam / adagrad row
+        kernels touch only the named rows — absent rows keep their weight
+        and their state. Plain sgd with wd == 0 takes the row kernel
+        regardless: its dense update leaves a zero-gradient row of a
+        finite weight unchanged, so the result is the same. Every other
+        case scatters into a zeroed dense gradient and runs update(),
+        i.e. the dense arithmetic. step_count advances once per call,
+        also for an empty id list (the reference runs ApplyUpdates on an
+        empty push)."""
+        s = self.spec
+        lazy = (s.lazy_update and s.name in self._ROW_KERNELS) \
+            or (s.name == "sgd" and s.wd == 0.0)
+        if not lazy:
+            dense = self._dense_grad.get(key)
+            if dense is None or dense.shape != w2d.shape \
+                    or dense.device != w2d.device:
+                dense = self._dense_grad[key] = torch.zeros_like(w2d)
+            ops.rsp_scatter(dense, ids, rows)
+            self.update(key, w2d.reshape(-1), dense.reshape(-1), rescale)
+            # restore the all-zero invariant by clearing the touched rows
+            # only: no full pass over the buffer per push
+            ops.rsp_scatter(dense, ids, torch.zeros_like(rows))
+            return
+        rs = s.rescale_grad if rescale is None else rescale
+        if s.clip_gradient is not None:
+            rows = torch.clamp(rows * rs, -s.clip_gradient, s.clip_gradient)
+            rs = 1.0
+        st = self._get_state(key, w2d.reshape(-1))
+        self.step_count[key] += 1
+        t = self.step_count[key]
+        if ids.numel() == 0:
+            return
+        if s.name == "sgd":
+            ops.rsp_sgd_update(w2d, ids, rows, s.lr, s.wd, rs)
+        elif s.name == "sgd_mom":
+            ops.rsp_sgd_mom_update(w2d, ids, rows, st["mom"].view_as(w2d),
+                                   s.lr, s.momentum, s.wd, rs)
+        elif s.name == "adam":
+            ops.rsp_adam_update(w2d, ids, rows, st["m"].view_as(w2d),
+                                st["v"].view_as(w2d), t, s.lr, s.beta1,
+                                s.beta2, s.eps, s.wd, rs)
+        elif s.name == "adagrad":
+            ops.rsp_adagrad_update(w2d, ids, rows, st["n"].view_as(w2d),
+                                   s.lr, s.eps, s.wd, rs)
 
     # -- checkpointing (kvstore.save_optimizer_states layout: a separate
     #    optimizer-state blob, python/mxnet/kvstore.py:566-592) ----------

@@ -324,3 +324,77 @@ def dcasgd_update(w, g, prev_w, mom, lr, lamda=0.04, momentum=0.0, wd=0.0,
             lr, lamda, momentum, wd, rescale)
         return
     ref.dcasgd_update(w, g, prev_w, mom, lr, lamda, momentum, wd, rescale)
+
+
+# ---------------------------------------------------------------------------
+# Row-sparse push: duplicate merge, row scatter, row-indexed updates.
+# Tables, states and merged rows are 2-d [rows][width] fp32; ids are int64.
+# Ids outside [0, rows) (the -1 padding included) are skipped.
+# ---------------------------------------------------------------------------
+
+def rsp_merge(ids: torch.Tensor, vals: torch.Tensor
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Sum duplicate rows deterministically (ascending original position).
+    Returns (out_ids[nnz], out_vals[nnz][width]): unique ids ascending,
+    unused tail slots id -1 / zero rows. The outputs are sized by the
+    upper bound nnz, so the GPU path never reads a count to the host."""
+    if _on_gpu(ids, vals):
+        g = _require_native()
+        ids = ids.reshape(-1).long()
+        nnz = ids.numel()
+        if vals.dim() != 2:
+            vals = vals.reshape(nnz, -1)
+        vals = vals.float().contiguous()
+        out_ids = torch.full((nnz,), -1, dtype=torch.int64,
+                             device=vals.device)
+        out_vals = torch.zeros_like(vals)
+        if nnz == 0:
+            return out_ids, out_vals
+        sorted_ids, perm = torch.sort(ids, stable=True)
+        head = torch.zeros_like(sorted_ids)
+        head[1:] = sorted_ids[1:] != sorted_ids[:-1]
+        seg = torch.cumsum(head, 0)  # seg[p] = unique index of position p
+        g.rsp_merge(sorted_ids, perm, seg, vals, out_ids, out_vals)
+        return out_ids, out_vals
+    return ref.rsp_merge(ids, vals)
+
+
+def rsp_scatter(dense, ids, merged, accumulate=False):
+    if _on_gpu(dense):
+        _require_native().rsp_scatter(dense, ids, merged, accumulate)
+        return
+    ref.rsp_scatter(dense, ids, merged, accumulate)
+
+
+def rsp_sgd_update(w, ids, merged, lr, wd=0.0, rescale=1.0):
+    if _on_gpu(w):
+        _require_native().rsp_sgd_update(w, ids, merged, lr, wd, rescale)
+        return
+    ref.rsp_sgd_update(w, ids, merged, lr, wd, rescale)
+
+
+def rsp_sgd_mom_update(w, ids, merged, mom, lr, momentum=0.9, wd=0.0,
+                       rescale=1.0):
+    if _on_gpu(w):
+        _require_native().rsp_sgd_mom_update(w, ids, merged, mom, lr,
+                                             momentum, wd, rescale)
+        return
+    ref.rsp_sgd_mom_update(w, ids, merged, mom, lr, momentum, wd, rescale)
+
+
+def rsp_adam_update(w, ids, merged, m, v, t, lr, beta1=0.9, beta2=0.999,
+                    eps=1e-8, wd=0.0, rescale=1.0):
+    if _on_gpu(w):
+        _require_native().rsp_adam_update(w, ids, merged, m, v, t, lr, beta1,
+                                          beta2, eps, wd, rescale)
+        return
+    ref.rsp_adam_update(w, ids, merged, m, v, t, lr, beta1, beta2, eps, wd,
+                        rescale)
+
+
+def rsp_adagrad_update(w, ids, merged, h, lr, eps=1e-7, wd=0.0, rescale=1.0):
+    if _on_gpu(w):
+        _require_native().rsp_adagrad_update(w, ids, merged, h, lr, eps, wd,
+                                             rescale)
+        return
+    ref.rsp_adagrad_update(w, ids, merged, h, lr, eps, wd, rescale)

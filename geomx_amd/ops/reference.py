@@ -331,3 +331,96 @@ def dcasgd_update(w: torch.Tensor, g: torch.Tensor, prev_w: torch.Tensor,
         upd = mom
     prev_w.copy_(w)
     w.add_(upd)
+
+
+# ---------------------------------------------------------------------------
+# Row-sparse push references (AccumulateRowSparseGrads + lazy row updates,
+# kvstore_dist_server.h:571; golden models of csrc/rowsparse.hip)
+# ---------------------------------------------------------------------------
+
+def rsp_merge(ids: torch.Tensor, vals: torch.Tensor
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Sum duplicate rows. Returns (out_ids[nnz], out_vals[nnz][width]):
+    the unique ids ascending with one summed row each, the unused tail
+    padded with id -1 and zero rows. Each sum adds the duplicates ONE BY
+    ONE in ascending original position (stable sort) — an explicit loop,
+    not index_add_, whose accumulation order is unspecified."""
+    ids = ids.reshape(-1).long()
+    nnz = ids.numel()
+    if vals.dim() != 2:  # (reshape(0, -1) is ambiguous, so only when needed)
+        vals = vals.reshape(nnz, -1)
+    vals = vals.float()
+    out_ids = torch.full((nnz,), -1, dtype=torch.int64, device=ids.device)
+    out_vals = torch.zeros_like(vals)
+    if nnz == 0:
+        return out_ids, out_vals
+    sorted_ids, perm = torch.sort(ids, stable=True)
+    sid, perm = sorted_ids.tolist(), perm.tolist()
+    u, p = 0, 0
+    while p < nnz:
+        acc = vals[perm[p]].clone()
+        q = p + 1
+        while q < nnz and sid[q] == sid[p]:
+            acc += vals[perm[q]]
+            q += 1
+        out_ids[u] = sid[p]
+        out_vals[u] = acc
+        u, p = u + 1, q
+    return out_ids, out_vals
+
+
+def _rsp_valid(ids: torch.Tensor, rows: int):
+    """(slot indices, row ids) of the in-range entries; ids outside
+    [0, rows) — the -1 padding included — are skipped."""
+    ids = ids.reshape(-1).long()
+    keep = ((ids >= 0) & (ids < rows)).nonzero().reshape(-1)
+    return keep, ids[keep]
+
+
+def rsp_scatter(dense: torch.Tensor, ids: torch.Tensor, merged: torch.Tensor,
+                accumulate: bool = False):
+    """dense[ids[u]] = merged[u] (or += with accumulate) for UNIQUE ids."""
+    keep, r = _rsp_valid(ids, dense.shape[0])
+    if accumulate:
+        dense[r] = dense[r] + merged[keep]
+    else:
+        dense[r] = merged[keep]
+
+
+def _rsp_apply(fn, w, ids, merged, states):
+    """Run a dense reference update on the gathered touched rows and
+    write them back; every other row of w and of the states is untouched."""
+    keep, r = _rsp_valid(ids, w.shape[0])
+    if r.numel() == 0:
+        return
+    wr = w[r]
+    sr = [s[r] for s in states]
+    fn(wr, merged[keep], *sr)
+    w[r] = wr
+    for s, x in zip(states, sr):
+        s[r] = x
+
+
+def rsp_sgd_update(w, ids, merged, lr, wd=0.0, rescale=1.0):
+    _rsp_apply(lambda wr, g: sgd_update(wr, g, lr, wd, rescale),
+               w, ids, merged, [])
+
+
+def rsp_sgd_mom_update(w, ids, merged, mom, lr, momentum=0.9, wd=0.0,
+                       rescale=1.0):
+    _rsp_apply(lambda wr, g, m: sgd_mom_update(wr, g, m, lr, momentum, wd,
+                                               rescale),
+               w, ids, merged, [mom])
+
+
+def rsp_adam_update(w, ids, merged, m, v, t, lr, beta1=0.9, beta2=0.999,
+                    eps=1e-8, wd=0.0, rescale=1.0):
+    _rsp_apply(lambda wr, g, mr, vr: adam_update(wr, g, mr, vr, t, lr, beta1,
+                                                 beta2, eps, wd, rescale),
+               w, ids, merged, [m, v])
+
+
+def rsp_adagrad_update(w, ids, merged, h, lr, eps=1e-7, wd=0.0, rescale=1.0):
+    _rsp_apply(lambda wr, g, hr: adagrad_update(wr, g, hr, lr, eps, wd,
+                                                rescale),
+               w, ids, merged, [h])

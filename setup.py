@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "geomx_amd/csrc/conv.hip",
         "geomx_amd/csrc/convwrw2.hip",
         "geomx_amd/csrc/fc.hip",
+        "geomx_amd/csrc/rowsparse.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
