@@ -341,14 +341,109 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool_nhwc(
 }
 
 
-// v2 of the fused conv1 stage: the block stages its 6 input rows ONCE
-// into LDS (16B LDS-DMA granules, straight [pix][4] copy) and the 4
-// waves split the width tiles, reading A fragments with ds_read_b128
-// from LDS instead of re-issuing overlapping global loads per lane
-// (the v1 kernel is global-load latency bound: every lane re-reads the
-// 5x5 window of its pixel from L1/L2).
+// ---------------------------------------------------------------------
+// LDS-staged forms of the fused conv + bias + ReLU + max-pool stage:
+// k_conv5_pool2_nhwc (conv1, CI = 4 padded, CO = 16) and
+// k_conv5_pool16_nhwc (conv2, CI = 16, CO = 16 / 32). Both are
+// persistent: a block is FOUR conv rows (two pooled rows) of one image,
+// staged once as 8 input rows by LDS-DMA (16 B granules, straight NHWC
+// copy) into one of two row images. The 4 waves split the 16-pixel
+// tiles and read A fragments from LDS; the weight fragments stay in
+// registers for the whole loop.
+//
+//   top of a block:   wait for this block's image, barrier
+//                     issue the NEXT block's DMA into the other image
+//                     store the PREVIOUS block's packed results
+//                     MFMA phase, pool, pack into registers
+//
+// so neither the staging round trip nor the stores sit in front of an
+// MFMA phase, and there is one barrier per block (it also orders the
+// previous phase's reads of the other image before the DMA that
+// overwrites it). With an odd number of pooled rows the last block of
+// an image stages 6 rows and stores one pooled row; its lower two conv
+// rows read older LDS data into accumulators that are never stored.
+//
+// Every accumulator (conv row, tile, co-tile) receives chunks km =
+// 0..nK-1 in ascending order with the fragment contents of the 2-row
+// kernels these replace (and of k_conv5_pool_nhwc), so out and mask are
+// bit-identical to theirs.
+// ---------------------------------------------------------------------
 __device__ __attribute__((aligned(64))) bf16_t g_convp_zeros[1024];
 
+// One 1 KiB LDS-DMA piece (16 B per lane) that the compiler does not
+// see: for a __builtin_amdgcn_global_load_lds in flight hipcc puts
+// s_waitcnt vmcnt(0) ahead of the next LDS read, which would end the
+// prefetch of the next block's image at the first fragment read of this
+// one (same device as convwrw2.hip). The kernels wait for their pieces
+// themselves. `lds_dst` is the wave-uniform LDS byte address.
+__device__ __forceinline__ void glds16_unseen(const void* gsrc,
+                                              unsigned lds_dst) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
+      : "memory");
+}
+
+// bias-added 2x2 window (q0..q3 = (dy,dx) (0,0) (0,1) (1,0) (1,1)) ->
+// pooled bf16 and argmax code; the first maximum wins, <= 0 clamps
+__device__ __forceinline__ void pool_relu4(float q0, float q1, float q2,
+                                           float q3, unsigned& ov,
+                                           unsigned& code) {
+  float mx = q0;
+  unsigned arg = 0;
+  if (q1 > mx) { mx = q1; arg = 1; }
+  if (q2 > mx) { mx = q2; arg = 2; }
+  if (q3 > mx) { mx = q3; arg = 3; }
+  if (mx <= 0.0f) {
+    ov = 0u;
+    code = 255u;
+  } else {
+    ov = cf2bf(mx);
+    code = arg;
+  }
+}
+
+// 4x4 transpose of 16-bit values inside each lane quad (the exchange of
+// the dgrad epilogue): every lane passes v0..v3 for ITS channel m; lane
+// j = m & 3 of the quad returns v_j of channels (m & ~3) .. +3, packed
+// low to high. All 64 lanes must be active.
+__device__ __forceinline__ uint2 quad_tr4(unsigned v0, unsigned v1,
+                                          unsigned v2, unsigned v3, int m) {
+  const unsigned sel1 = (m & 1) ? 0x03020706u : 0x05040100u;
+  const bool lo2 = (m & 3) < 2;
+  const unsigned a = v0 | (v1 << 16);
+  const unsigned b = v2 | (v3 << 16);
+  const unsigned a1 = __builtin_amdgcn_perm(
+      (unsigned)__builtin_amdgcn_mov_dpp((int)a, 0xB1, 0xF, 0xF, true), a,
+      sel1);
+  const unsigned b1 = __builtin_amdgcn_perm(
+      (unsigned)__builtin_amdgcn_mov_dpp((int)b, 0xB1, 0xF, 0xF, true), b,
+      sel1);
+  const unsigned snd = lo2 ? b1 : a1;
+  const unsigned rcv =
+      (unsigned)__builtin_amdgcn_mov_dpp((int)snd, 0x4E, 0xF, 0xF, true);
+  return make_uint2(lo2 ? a1 : rcv, lo2 ? rcv : b1);
+}
+
+// four 16-bit codes (quad_tr4 of codes) -> four bytes
+__device__ __forceinline__ unsigned pack_codes(uint2 c) {
+  return __builtin_amdgcn_perm(c.y, c.x, 0x06040200u);
+}
+
+// conv1 stage. A tile's chunk km reads, per conv row, 16 B at pixel wo
+// of staged row r + kh (two ds_read_b64: odd wo is only 8 B aligned);
+// slots past S hit the next pixel's data, zeroed by the Sp padding in
+// w_frags. The walk is flattened over (tile, km): the reads of the next
+// step are issued before the 4 MFMAs (one per conv row) of this one,
+// across tiles too. A lane pools to 2 pixels x 2 pooled rows of channel
+// m; quad_tr4 turns them into 4 channels of one (pooled row, pixel):
+// one 8-byte out store and one 4-byte mask store per lane and tile.
 template <int PIX>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
     const bf16_t* __restrict__ in,       // [N][Hi][Wi][4]
@@ -366,14 +461,18 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   constexpr int AROW_BYTES = PIX * CI * 2;
   constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
   constexpr int ARPB = NCHA * 1024 + 64;  // bank skew per row
-  constexpr int NROW = 6;                 // 2 conv rows + 4 halo
-  __shared__ __attribute__((aligned(128))) char lds_rows[NROW * ARPB];
+  constexpr int ROWS = 4;                 // conv rows per block
+  constexpr int NROW = ROWS + 4;
+  constexpr int IMG = NROW * ARPB;
+  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;  // tiles per wave
+  constexpr int NS = MAXU * nK;                   // steps of the walk
+  __shared__ __attribute__((aligned(128))) char lds_rows[2 * IMG];
 
   const int lane = threadIdx.x & 63;
   const int p = lane & 15;
   const int q = lane >> 4;
   const int m = lane & 15;
-  const int wid = threadIdx.x >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   bf16x8 breg[nK];
 #pragma unroll
@@ -383,110 +482,166 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
 
   const int Hop = Ho >> 1, Wop = Wo >> 1;
   const int tiles_w = (Wo + 15) >> 4;
-  const long long n_blocks = (long long)Nn * Hop;
+  const int hblocks = (Hop + 1) >> 1;
+  const long long n_blocks = (long long)Nn * hblocks;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
   const unsigned lds0 =
       (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_rows;
 
-  for (long long blk = wg; blk < n_blocks; blk += n_wg) {
-    const int hp = (int)(blk % Hop);
-    const long long n = blk / Hop;
-    const int ho0 = hp * 2;
-    // ---- stage the 6 input rows
-    for (int t = wid; t < NROW * NCHA; t += 4) {
+  // per-lane read address of (tile u, chunk km) in image 0, conv row 0.
+  // A tile past the row clamps to the last pixel: in-bounds, never
+  // stored. The one k-run past K (km 3, q 3) must be ZERO: those lanes
+  // read the last 16 bytes of the row's staged kilobytes instead, which
+  // lie past pixel PIX and are zero-filled in every staged row (a select
+  // after the read cost 16 VALU per tile, 0.007 ms at the flagship).
+  static_assert((nK - 1) * 32 + 2 * 8 < K && (nK - 1) * 32 + 3 * 8 >= K, "");
+  static_assert(AROW_BYTES + 16 <= NCHA * 1024, "zero tail behind the row");
+  unsigned aofs[MAXU][nK];
+#pragma unroll
+  for (int u = 0; u < MAXU; ++u) {
+    const int wo_raw = ((wid + 4 * u) << 4) + p;
+    const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
+#pragma unroll
+    for (int km = 0; km < nK; ++km) {
+      const int k0 = km * 32 + q * 8;
+      aofs[u][km] = lds0 + (k0 < K ? (unsigned)(wo * (CI * 2) +
+                                                (k0 / Sp) * ARPB +
+                                                (k0 % Sp) * 2)
+                                   : (unsigned)(NCHA * 1024 - 16));
+    }
+  }
+
+  auto stage = [&](long long b, int img) {
+    const long long n = b / hblocks;
+    const int ho0 = (int)(b - n * hblocks) * ROWS;
+    const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
+    const int nst = (nrows + 4) * NCHA;
+    for (int t = wid; t < nst; t += 4) {
       const int ir = t / NCHA;
       const int c = t - ir * NCHA;
-      const int slot = c * 64 + lane;      // 16B = 2 pixels
-      const int pix = slot * 2;
+      const int pix = (c * 64 + lane) * 2;   // 16B = 2 pixels
       const bf16_t* src =
           (pix + 1 < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
                                  (long long)pix * CI)
                          : g_convp_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_rows + ir * ARPB +
-                                                    c * 1024),
-          16, 0, 0);
+      glds16_unseen(src, lds0 + img * IMG + ir * ARPB + c * 1024);
     }
+  };
+
+  // packed results of one block: lane j = m & 3 holds channels
+  // (m & ~3)..+3 of pooled row j >> 1, pooled pixel 2q + (j & 1) of tile u
+  uint2 pko[MAXU];
+  unsigned pkm[MAXU];
+  auto flush = [&](long long n, int hb, int npr) {
+    const int pr = (m & 3) >> 1;
+    if (pr >= npr) return;
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      const int wp = ((wid + 4 * u) << 3) + q * 2 + (m & 1);
+      if (wp < Wop) {
+        const long long off =
+            ((n * Hop + (hb * 2 + pr)) * (long long)Wop + wp) * CO + (m & ~3);
+        *reinterpret_cast<uint2*>(out + off) = pko[u];
+        *reinterpret_cast<unsigned*>(mask + off) = pkm[u];
+      }
+    }
+  };
+
+  long long blk = wg;
+  int img = 0;
+  if (blk < n_blocks) stage(blk, 0);
+  long long pn = 0;
+  int phb = 0, pnpr = 0;
+  for (; blk < n_blocks; blk += n_wg, img ^= 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (blk + n_wg < n_blocks) stage(blk + n_wg, img ^ 1);
+    flush(pn, phb, pnpr);
 
-    const long long out_row =
-        ((long long)n * Hop + hp) * (long long)Wop * CO;
-    for (int tw = wid; tw < tiles_w; tw += 4) {
-      const int wo_raw = (tw << 4) + p;
-      const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      f32x4 a0 = (f32x4)0.0f, a1 = (f32x4)0.0f;
+    const long long n = blk / hblocks;
+    const int hb = (int)(blk - n * hblocks);
+    const unsigned ib = (unsigned)(img * IMG);
+    auto ldk = [&](bf16x8(&d)[ROWS], int u, int km) {
+      const unsigned a = aofs[u][km] + ib;
+      typedef __attribute__((ext_vector_type(2))) unsigned uu2;
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        union { struct { uu2 lo, hi; } p; bf16x8 h; } c;
+        c.p.lo = *(const __attribute__((address_space(3)))
+                   uu2*)(uintptr_t)(a + r * ARPB);
+        c.p.hi = *(const __attribute__((address_space(3)))
+                   uu2*)(uintptr_t)(a + r * ARPB + 8);
+        d[r] = c.h;
+      }
+    };
+    bf16x8 f[2][ROWS];
+    ldk(f[0], 0, 0);
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+      if (wid + 4 * u >= tiles_w) break;
+      f32x4 acc[ROWS];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) acc[r] = (f32x4)0.0f;
 #pragma unroll
       for (int km = 0; km < nK; ++km) {
-        const int k0 = km * 32 + q * 8;
-        const int kh = k0 / Sp;
-        const int j0 = k0 % Sp;
-        bf16x8 f0 = (bf16x8)0, f1 = (bf16x8)0;
-        if (k0 < K && j0 < S) {
-          // contiguous within the row span; slots past S hit the next
-          // pixel's data, zeroed by the Sp padding in w_frags. Odd wo
-          // makes the address 8B-aligned only: two b64 reads.
-          const unsigned off = (unsigned)(wo * (CI * 2) + j0 * 2);
-          typedef __attribute__((ext_vector_type(2))) unsigned uu2;
-          union { struct { uu2 lo, hi; } p; bf16x8 h; } c0, c1;
-          c0.p.lo = *(const __attribute__((address_space(3)))
-                      uu2*)(uintptr_t)(lds0 + kh * ARPB + off);
-          c0.p.hi = *(const __attribute__((address_space(3)))
-                      uu2*)(uintptr_t)(lds0 + kh * ARPB + off + 8);
-          c1.p.lo = *(const __attribute__((address_space(3)))
-                      uu2*)(uintptr_t)(lds0 + (kh + 1) * ARPB + off);
-          c1.p.hi = *(const __attribute__((address_space(3)))
-                      uu2*)(uintptr_t)(lds0 + (kh + 1) * ARPB + off + 8);
-          f0 = c0.h;
-          f1 = c1.h;
-        }
-        a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f0, breg[km], a0,
-                                                     0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, breg[km], a1,
-                                                     0, 0, 0);
-      }
-      const int wo0 = tw << 4;
+        const int s = u * nK + km;
+        if (s + 1 < NS) ldk(f[(s + 1) & 1], (s + 1) / nK, (s + 1) % nK);
+        // (fenced: left alone, the scheduler sinks the reads to their
+        // MFMAs; 0.003-0.005 ms at the flagship)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int pi = 0; pi < 2; ++pi) {
-        const int i0 = pi * 2;
-        const int wp = (wo0 + q * 4 + i0) >> 1;
-        if (wp >= Wop) continue;
-        const float q0 = a0[i0] + bias_v;
-        const float q1 = a0[i0 + 1] + bias_v;
-        const float q2 = a1[i0] + bias_v;
-        const float q3 = a1[i0 + 1] + bias_v;
-        float mx = q0;
-        int arg = 0;
-        if (q1 > mx) { mx = q1; arg = 1; }
-        if (q2 > mx) { mx = q2; arg = 2; }
-        if (q3 > mx) { mx = q3; arg = 3; }
-        bf16_t ov;
-        uint8_t code;
-        if (mx <= 0.0f) {
-          ov = (bf16_t)0;
-          code = 255;
-        } else {
-          ov = cf2bf(mx);
-          code = (uint8_t)arg;
-        }
-        const long long o_off = out_row + (long long)wp * CO + m;
-        out[o_off] = ov;
-        mask[o_off] = code;
+        for (int r = 0; r < ROWS; ++r)
+          acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              f[s & 1][r], breg[km], acc[r], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
+      // conv pixel = tile*16 + q*4 + i: horizontal pairs are (i, i+1) of
+      // one lane, vertical pairs two accumulators
+      unsigned ov[2][2], cd[2][2];
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+        for (int pi = 0; pi < 2; ++pi)
+          pool_relu4(acc[2 * pr][2 * pi] + bias_v,
+                     acc[2 * pr][2 * pi + 1] + bias_v,
+                     acc[2 * pr + 1][2 * pi] + bias_v,
+                     acc[2 * pr + 1][2 * pi + 1] + bias_v, ov[pr][pi],
+                     cd[pr][pi]);
+      pko[u] = quad_tr4(ov[0][0], ov[0][1], ov[1][0], ov[1][1], m);
+      pkm[u] = pack_codes(quad_tr4(cd[0][0], cd[0][1], cd[1][0], cd[1][1], m));
     }
-    __syncthreads();
+    pn = n;
+    phb = hb;
+    pnpr = (Ho - hb * ROWS) < ROWS ? 1 : 2;
   }
+  flush(pn, phb, pnpr);
 }
 
 
-// CI=16 fused conv+bias+relu+pool (conv2 stage, CO = COT*16): like the
-// CI=4 v2 but the weight fragments live in LDS (26.6 KB for 16->32),
-// staged ONCE before the persistent block loop (w_frags are
-// block-invariant), and A-fragment reads are 16B-aligned b128.
+// conv2 stage (CO = COT*16). With CI = 16 a tap row is 80 K-slots = 2.5
+// chunks, so along K a conv row's operand is the row image read linearly
+// from its first staged row: "linear fragment" t of row parity par is
+// k-run t*32 + q*8 counted from staged row par, and
+//
+//     A(row par,     chunk km) = F(par, km)
+//     A(row par + 2, chunk km) = F(par, km + 5)
+//
+// Rows par and par + 2 share one walk over t = 0..17 (18 ds_read_b128
+// for 26*COT MFMAs; the 2-row kernel read 26 A and 26*COT B fragments
+// for them). Chunk 12 is the exception: its k-runs q >= 2 lie past K
+// and must be ZERO (the staged data there is finite only by luck), but
+// F(par, 12) is also chunk 7 of row par + 2, which needs the real data.
+// The walk therefore feeds chunk 12 a copy with lanes q >= 2 zeroed
+// (t = 12 for row par, t = 17 for row par + 2). F(1, 17) of those lanes
+// would lie one row past the image: the image pair is followed by one
+// spare row, so the read stays inside the allocation.
+// The COT*13 weight fragments live in registers (104 VGPRs at COT = 2);
+// two 8-row images of 4160 B rows + the spare row are 70.7 KB, 2
+// workgroups per CU. Reads run two steps ahead of their MFMAs through
+// both parities and into the wave's next tile.
 template <int COT, int PIX>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool16_nhwc(
+__global__ __launch_bounds__(CONV_THREADS, 2) void k_conv5_pool16_nhwc(
     const bf16_t* __restrict__ in,       // [N][Hi][Wi][16]
     const bf16_t* __restrict__ w_frags,  // [COT][nK][64][8]
     const float* __restrict__ bias,      // [CO] or nullptr
@@ -494,31 +649,32 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool16_nhwc(
     uint8_t* __restrict__ mask,          // [N*Hop*Wop*CO]
     int Nn, int Hi, int Wi, int Ho, int Wo) {
   constexpr int CI = 16;
-  constexpr int S = 5 * CI;             // 80
-  constexpr int Sp = S;                 // already a multiple of 8
-  constexpr int K = 5 * Sp;             // 400
+  constexpr int S = 5 * CI;             // 80, already a multiple of 8
+  constexpr int K = 5 * S;              // 400
   constexpr int nK = (K + 31) / 32;     // 13
   constexpr int CO = COT * 16;
   constexpr int AROW_BYTES = PIX * CI * 2;
   constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
   constexpr int ARPB = NCHA * 1024 + 64;
-  constexpr int NROW = 6;
-  constexpr int BBYTES = COT * nK * 64 * 16;
-  __shared__ __attribute__((aligned(128))) char lds_all[NROW * ARPB +
-                                                        BBYTES];
-  constexpr int BOFF = NROW * ARPB;
+  constexpr int ROWS = 4;
+  constexpr int NROW = ROWS + 4;
+  constexpr int IMG = NROW * ARPB;
+  constexpr int NT = nK + 5;            // linear fragments per parity
+  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;
+  constexpr int NS = MAXU * 2 * NT;     // steps of the walk
+  static_assert(NT % 3 == 0, "three fragment sets rotate per parity");
+  __shared__ __attribute__((aligned(128))) char lds_all[2 * IMG + ARPB];
 
   const int lane = threadIdx.x & 63;
   const int p = lane & 15;
   const int q = lane >> 4;
   const int m = lane & 15;
-  const int wid = threadIdx.x >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
-  // stage the weight panel once (block-invariant across the loop)
-  for (int t = threadIdx.x; t < COT * nK * 64; t += blockDim.x) {
-    reinterpret_cast<uint4*>(lds_all + BOFF)[t] =
-        reinterpret_cast<const uint4*>(w_frags)[t];
-  }
+  bf16x8 breg[COT * nK];
+#pragma unroll
+  for (int i = 0; i < COT * nK; ++i)
+    breg[i] = *reinterpret_cast<const bf16x8*>(w_frags + (i * 64 + lane) * 8);
   float bias_v[COT];
 #pragma unroll
   for (int ct = 0; ct < COT; ++ct)
@@ -526,104 +682,175 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool16_nhwc(
 
   const int Hop = Ho >> 1, Wop = Wo >> 1;
   const int tiles_w = (Wo + 15) >> 4;
-  const long long n_blocks = (long long)Nn * Hop;
+  const int hblocks = (Hop + 1) >> 1;
+  const long long n_blocks = (long long)Nn * hblocks;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
   const unsigned lds0 =
       (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_all;
-  const bf16x8* lds_bv =
-      reinterpret_cast<const bf16x8*>(lds_all + BOFF) + lane;
 
-  for (long long blk = wg; blk < n_blocks; blk += n_wg) {
-    const int hp = (int)(blk % Hop);
-    const long long n = blk / Hop;
-    const int ho0 = hp * 2;
-    for (int t = wid; t < NROW * NCHA; t += 4) {
+  // linear fragment t sits at foff[t % 5] + 2 * (t / 5) rows
+  unsigned foff[5];
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    const int k0 = t * 32 + q * 8;
+    foff[t] = (unsigned)((k0 / S) * ARPB + (k0 % S) * 2);
+  }
+  const bool qlo = q < 2;
+  unsigned wofs[MAXU];
+#pragma unroll
+  for (int u = 0; u < MAXU; ++u) {
+    const int wo_raw = ((wid + 4 * u) << 4) + p;
+    wofs[u] = lds0 + (unsigned)((wo_raw < Wo ? wo_raw : (Wo - 1)) * (CI * 2));
+  }
+
+  auto stage = [&](long long b, int img) {
+    const long long n = b / hblocks;
+    const int ho0 = (int)(b - n * hblocks) * ROWS;
+    const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
+    const int nst = (nrows + 4) * NCHA;
+    for (int t = wid; t < nst; t += 4) {
       const int ir = t / NCHA;
       const int c = t - ir * NCHA;
       const int slot = c * 64 + lane;      // 16B = half a pixel
-      const int pix = slot >> 1;
       const bf16_t* src =
-          (pix < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                             (long long)slot * 8)
-                     : g_convp_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all + ir * ARPB +
-                                                    c * 1024),
-          16, 0, 0);
+          ((slot >> 1) < Wi)
+              ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
+                      (long long)slot * 8)
+              : g_convp_zeros;
+      glds16_unseen(src, lds0 + img * IMG + ir * ARPB + c * 1024);
     }
+  };
+
+  // packed results of one block, lane j = m & 3 of a quad, channels
+  // (m & ~3)..+3. COT = 2: [u][pooled row], pixel 2q + (j >> 1) of
+  // co-tile j & 1. COT = 1: [u][0], pooled row j >> 1, pixel 2q + (j & 1).
+  uint2 pko[MAXU][COT];
+  unsigned pkm[MAXU][COT];
+  auto flush = [&](long long n, int hb, int npr) {
+    const int j = m & 3;
+#pragma unroll
+    for (int u = 0; u < MAXU; ++u) {
+#pragma unroll
+      for (int e = 0; e < COT; ++e) {
+        const int pr = COT == 2 ? e : (j >> 1);
+        const int pi = COT == 2 ? (j >> 1) : (j & 1);
+        const int ch = (COT == 2 ? (j & 1) * 16 : 0) + (m & ~3);
+        const int wp = ((wid + 4 * u) << 3) + q * 2 + pi;
+        if (pr < npr && wp < Wop) {
+          const long long off =
+              ((n * Hop + (hb * 2 + pr)) * (long long)Wop + wp) * CO + ch;
+          *reinterpret_cast<uint2*>(out + off) = pko[u][e];
+          *reinterpret_cast<unsigned*>(mask + off) = pkm[u][e];
+        }
+      }
+    }
+  };
+
+  long long blk = wg;
+  int img = 0;
+  if (blk < n_blocks) stage(blk, 0);
+  long long pn = 0;
+  int phb = 0, pnpr = 0;
+  for (; blk < n_blocks; blk += n_wg, img ^= 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (blk + n_wg < n_blocks) stage(blk + n_wg, img ^ 1);
+    flush(pn, phb, pnpr);
 
-    const long long out_row =
-        ((long long)n * Hop + hp) * (long long)Wop * CO;
-    for (int tw = wid; tw < tiles_w; tw += 4) {
-      const int wo_raw = (tw << 4) + p;
-      const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      f32x4 a0[COT], a1[COT];
+    const long long n = blk / hblocks;
+    const int hb = (int)(blk - n * hblocks);
+    const unsigned ib = (unsigned)(img * IMG);
+    // 5 read bases per tile; every other address is an immediate offset
+    // from one of them. (Opaque to the compiler, which otherwise keeps
+    // one loop-invariant address register per read of the walk: 72.)
+    unsigned fb[MAXU][5];
 #pragma unroll
-      for (int ct = 0; ct < COT; ++ct) {
-        a0[ct] = (f32x4)0.0f;
-        a1[ct] = (f32x4)0.0f;
+    for (int u = 0; u < MAXU; ++u)
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        fb[u][j] = wofs[u] + ib + foff[j];
+        asm volatile("" : "+v"(fb[u][j]));
       }
-#pragma unroll 1
-      for (int km = 0; km < nK; ++km) {
-        const int k0 = km * 32 + q * 8;
-        const int kh = k0 / Sp;
-        const int j0 = k0 % Sp;
-        bf16x8 f0 = (bf16x8)0, f1 = (bf16x8)0;
-        if (k0 < K) {
-          const unsigned off = (unsigned)(wo * (CI * 2) + j0 * 2);
-          f0 = *(const __attribute__((address_space(3)))
-                 bf16x8*)(uintptr_t)(lds0 + kh * ARPB + off);
-          f1 = *(const __attribute__((address_space(3)))
-                 bf16x8*)(uintptr_t)(lds0 + (kh + 1) * ARPB + off);
-        }
+    // step s = (tile u, parity, t)
+    auto ldf = [&](int s) {
+      const int u = s / (2 * NT);
+      const int par = (s / NT) & 1;
+      const int t = s % NT;
+      return *(const __attribute__((address_space(3))) bf16x8*)(uintptr_t)(
+          fb[u][t % 5] + (par + 2 * (t / 5)) * ARPB);
+    };
+    bf16x8 f[3];
+    f[0] = ldf(0);
+    f[1] = ldf(1);
 #pragma unroll
-        for (int ct = 0; ct < COT; ++ct) {
-          const bf16x8 bf = lds_bv[(ct * nK + km) * 64];
-          a0[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f0, bf, a0[ct],
-                                                           0, 0, 0);
-          a1[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, bf, a1[ct],
-                                                           0, 0, 0);
-        }
-      }
-      const int wo0 = tw << 4;
+    for (int u = 0; u < MAXU; ++u) {
+      if (wid + 4 * u >= tiles_w) break;
+      f32x4 acc[ROWS][COT];
 #pragma unroll
-      for (int ct = 0; ct < COT; ++ct) {
+      for (int r = 0; r < ROWS; ++r)
 #pragma unroll
-        for (int pi = 0; pi < 2; ++pi) {
-          const int i0 = pi * 2;
-          const int wp = (wo0 + q * 4 + i0) >> 1;
-          if (wp >= Wop) continue;
-          const float q0 = a0[ct][i0] + bias_v[ct];
-          const float q1 = a0[ct][i0 + 1] + bias_v[ct];
-          const float q2 = a1[ct][i0] + bias_v[ct];
-          const float q3 = a1[ct][i0 + 1] + bias_v[ct];
-          float mx = q0;
-          int arg = 0;
-          if (q1 > mx) { mx = q1; arg = 1; }
-          if (q2 > mx) { mx = q2; arg = 2; }
-          if (q3 > mx) { mx = q3; arg = 3; }
-          bf16_t ov;
-          uint8_t code;
-          if (mx <= 0.0f) {
-            ov = (bf16_t)0;
-            code = 255;
-          } else {
-            ov = cf2bf(mx);
-            code = (uint8_t)arg;
+        for (int ct = 0; ct < COT; ++ct) acc[r][ct] = (f32x4)0.0f;
+#pragma unroll
+      for (int par = 0; par < 2; ++par) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const int s = (u * 2 + par) * NT + t;
+          if (s + 2 < NS) f[(s + 2) % 3] = ldf(s + 2);
+          // keeps the read two steps ahead (and not twenty: unfenced,
+          // the scheduler hoists reads until the registers run out)
+          __builtin_amdgcn_sched_barrier(0);
+          const bf16x8 cur = f[s % 3];
+          const bf16x8 curz = qlo ? cur : (bf16x8)0;
+          if (t < nK) {         // chunk t of conv row par
+#pragma unroll
+            for (int ct = 0; ct < COT; ++ct)
+              acc[par][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  t == nK - 1 ? curz : cur, breg[ct * nK + t], acc[par][ct],
+                  0, 0, 0);
           }
-          const long long o_off =
-              out_row + (long long)wp * CO + ct * 16 + m;
-          out[o_off] = ov;
-          mask[o_off] = code;
+          if (t >= 5) {         // chunk t - 5 of conv row par + 2
+#pragma unroll
+            for (int ct = 0; ct < COT; ++ct)
+              acc[par + 2][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  t == NT - 1 ? curz : cur, breg[ct * nK + t - 5],
+                  acc[par + 2][ct], 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
         }
+      }
+      unsigned ov[2][COT][2], cd[2][COT][2];
+#pragma unroll
+      for (int pr = 0; pr < 2; ++pr)
+#pragma unroll
+        for (int ct = 0; ct < COT; ++ct)
+#pragma unroll
+          for (int pi = 0; pi < 2; ++pi)
+            pool_relu4(acc[2 * pr][ct][2 * pi] + bias_v[ct],
+                       acc[2 * pr][ct][2 * pi + 1] + bias_v[ct],
+                       acc[2 * pr + 1][ct][2 * pi] + bias_v[ct],
+                       acc[2 * pr + 1][ct][2 * pi + 1] + bias_v[ct],
+                       ov[pr][ct][pi], cd[pr][ct][pi]);
+      if constexpr (COT == 2) {
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+          pko[u][pr] = quad_tr4(ov[pr][0][0], ov[pr][1][0], ov[pr][0][1],
+                                ov[pr][1][1], m);
+          pkm[u][pr] = pack_codes(quad_tr4(cd[pr][0][0], cd[pr][1][0],
+                                           cd[pr][0][1], cd[pr][1][1], m));
+        }
+      } else {
+        pko[u][0] = quad_tr4(ov[0][0][0], ov[0][0][1], ov[1][0][0],
+                             ov[1][0][1], m);
+        pkm[u][0] = pack_codes(quad_tr4(cd[0][0][0], cd[0][0][1],
+                                        cd[1][0][0], cd[1][0][1], m));
       }
     }
-    __syncthreads();
+    pn = n;
+    phb = hb;
+    pnpr = (Ho - hb * ROWS) < ROWS ? 1 : 2;
   }
+  flush(pn, phb, pnpr);
 }
 
 
@@ -1001,6 +1228,60 @@ static bool conv5_unpool_geometry_ok(const uint8_t* mask, int Hi, int Wi,
          !((Hi | Wi) & 1);
 }
 
+// Launch table of the fused conv + bias + ReLU + max-pool forward:
+// k_conv5_pool16_nhwc (CI=16, 120-pixel rows), k_conv5_pool2_nhwc (CI=4,
+// even Wi, 232-pixel rows) and the register-only k_conv5_pool_nhwc<4>
+// beyond. n_wg <= 0 picks the default grid. The LDS kernels work in
+// blocks of 2 pooled rows. pool16 is capped at the 512 workgroups that
+// are resident on 256 CUs (2 per CU, LDS-bound): each fetches its
+// weights once and walks a run of blocks with the next block's staging
+// in flight (the flagship's 13824 blocks are 27 per workgroup; 1024 and
+// 2048 measured 1-4 % slower). pool2 (4 per CU) measured best at two
+// resident rounds, 2048. Returns 0, or -1 when nothing serves the
+// geometry.
+static int conv5_pool_launch(const bf16_t* in, const bf16_t* w_frags,
+                             const float* bias, bf16_t* out, uint8_t* mask,
+                             int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
+                             int CO, int n_wg, hipStream_t s) {
+  if ((CO != 16 && CO != 32) || (Ho & 1) || (Wo & 1)) return -1;
+  const long long rows = (long long)Nn * (Ho >> 1);
+  const long long blocks = (long long)Nn * (((Ho >> 1) + 1) >> 1);
+  const dim3 block(CONV_THREADS);
+  const int W16 = (Wo + 15) >> 4;
+  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
+  auto grid_of = [&](long long cap) {
+    long long g = n_wg > 0 ? n_wg : (blocks < cap ? blocks : cap);
+    return dim3((unsigned)(g < 1 ? 1 : g));
+  };
+  if (CI == 16) {
+    if (CO == 32 && need <= 120) {
+      hipLaunchKernelGGL((k_conv5_pool16_nhwc<2, 120>), grid_of(512), block,
+                         0, s, in, w_frags, bias, out, mask, Nn, Hi, Wi,
+                         Ho, Wo);
+      return 0;
+    }
+    if (CO == 16 && need <= 120) {
+      hipLaunchKernelGGL((k_conv5_pool16_nhwc<1, 120>), grid_of(512), block,
+                         0, s, in, w_frags, bias, out, mask, Nn, Hi, Wi,
+                         Ho, Wo);
+      return 0;
+    }
+    return -1;
+  }
+  if (CI == 4 && !(Wi & 1) && need <= 232) {
+    hipLaunchKernelGGL((k_conv5_pool2_nhwc<232>), grid_of(2048), block, 0, s,
+                       in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo);
+    return 0;
+  }
+  if (CI == 4) {
+    const dim3 grid(n_wg > 0 ? n_wg : conv_blocks(rows));
+    hipLaunchKernelGGL((k_conv5_pool_nhwc<4>), grid, block, 0, s, in,
+                       w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo);
+    return 0;
+  }
+  return -1;
+}
+
 extern "C" {
 
 // Test hook: ALWAYS the direct kernel k_conv5_nhwc<32, 1> on a
@@ -1086,43 +1367,20 @@ int geops_conv5_pool_nhwc(const bf16_t* in, const bf16_t* w_frags,
                           const float* bias, bf16_t* out, uint8_t* mask,
                           int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
                           int CO, hipStream_t s) {
-  if ((CO != 16 && CO != 32) || (Ho & 1) || (Wo & 1)) return -1;
-  const long long rows = (long long)Nn * (Ho >> 1);
-  const dim3 grid(conv_blocks(rows)), block(CONV_THREADS);
-  if (CI == 16) {
-    const int W16 = (Wo + 15) >> 4;
-    const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
-    int n_wg = (int)((rows < 2048) ? rows : 2048);
-    if (CO == 32 && need <= 120) {
-      hipLaunchKernelGGL((k_conv5_pool16_nhwc<2, 120>), dim3(n_wg), block,
-                         0, s, in, w_frags, bias, out, mask, Nn, Hi, Wi,
-                         Ho, Wo);
-      return 0;
-    }
-    if (CO == 16 && need <= 120) {
-      hipLaunchKernelGGL((k_conv5_pool16_nhwc<1, 120>), dim3(n_wg), block,
-                         0, s, in, w_frags, bias, out, mask, Nn, Hi, Wi,
-                         Ho, Wo);
-      return 0;
-    }
-    return -1;
-  }
-  if (CI == 4 && !(Wi & 1)) {
-    const int W16 = (Wo + 15) >> 4;
-    const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
-    int n_wg = (int)((rows < 2048) ? rows : 2048);
-    if (need <= 232) {
-      hipLaunchKernelGGL((k_conv5_pool2_nhwc<232>), dim3(n_wg), block, 0, s,
-                         in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo);
-      return 0;
-    }
-  }
-  if (CI == 4) {
-    hipLaunchKernelGGL((k_conv5_pool_nhwc<4>), grid, block, 0, s, in,
-                       w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo);
-    return 0;
-  }
-  return -1;
+  return conv5_pool_launch(in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo,
+                           CI, CO, 0, s);
+}
+
+// Test hook: the launch table of geops_conv5_pool_nhwc on a grid of n_wg
+// workgroups, so that small inputs reach the persistent loop, the
+// cross-block prefetch and the one-pooled-row tail block.
+int geops_conv5_pool_nwg_nhwc(const bf16_t* in, const bf16_t* w_frags,
+                              const float* bias, bf16_t* out, uint8_t* mask,
+                              int Nn, int Hi, int Wi, int Ho, int Wo, int CI,
+                              int CO, int n_wg, hipStream_t s) {
+  if (n_wg < 1) return -1;
+  return conv5_pool_launch(in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo,
+                           CI, CO, n_wg, s);
 }
 
 void geops_pad_ch3to4_nhwc(const void* in, bf16_t* out, long long npix,

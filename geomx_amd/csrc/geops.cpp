@@ -84,6 +84,9 @@ int geops_conv5_nhwc(const unsigned short*, const unsigned short*,
 int geops_conv5_pool_nhwc(const unsigned short*, const unsigned short*,
                           const float*, unsigned short*, uint8_t*, int, int,
                           int, int, int, int, int, hipStream_t);
+int geops_conv5_pool_nwg_nhwc(const unsigned short*, const unsigned short*,
+                              const float*, unsigned short*, uint8_t*, int,
+                              int, int, int, int, int, int, int, hipStream_t);
 void geops_pad_ch3to4_nhwc(const void*, unsigned short*, long long, int,
                            hipStream_t);
 int geops_conv5_wrw16_nhwc(const unsigned short*, const unsigned short*,
@@ -354,6 +357,45 @@ void conv5_pool_nhwc(torch::Tensor in, torch::Tensor w_frags,
   TORCH_CHECK(rc == 0, "conv5_pool_nhwc: unsupported geometry CI=", CI,
               " CO=", CO);
   launch_check("conv5_pool_nhwc");
+}
+
+// Test hook: conv5_pool_nhwc on a grid of n_wg workgroups, with the
+// tensor sizes checked against the geometry.
+void conv5_pool_nwg_nhwc(torch::Tensor in, torch::Tensor w_frags,
+                         torch::Tensor bias, torch::Tensor out,
+                         torch::Tensor mask, int64_t N, int64_t Hi,
+                         int64_t Wi, int64_t Ho, int64_t Wo, int64_t CI,
+                         int64_t CO, int64_t n_wg) {
+  TORCH_CHECK(in.is_cuda() && w_frags.is_cuda() && out.is_cuda() &&
+              mask.is_cuda());
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16 &&
+              w_frags.scalar_type() == torch::kBFloat16 &&
+              out.scalar_type() == torch::kBFloat16 &&
+              mask.scalar_type() == torch::kUInt8);
+  TORCH_CHECK(N >= 1 && Ho >= 2 && Wo >= 2 && Hi == Ho + 4 && Wi == Wo + 4 &&
+              n_wg >= 1 && n_wg <= 65536 && (CI == 4 || CI == 16) &&
+              (CO == 16 || CO == 32),
+              "conv5_pool_nwg_nhwc: bad size or n_wg");
+  const int64_t Sp = (5 * CI + 7) & ~7, nK = (5 * Sp + 31) / 32;
+  TORCH_CHECK(in.numel() == N * Hi * Wi * CI &&
+              out.numel() == N * (Ho / 2) * (Wo / 2) * CO &&
+              mask.numel() == out.numel() &&
+              w_frags.numel() == (CO / 16) * nK * 64 * 8,
+              "conv5_pool_nwg_nhwc: tensor size mismatch");
+  const bool has_bias = bias.numel() > 0;
+  if (has_bias)
+    TORCH_CHECK(bias.scalar_type() == torch::kFloat32 && bias.is_cuda() &&
+                bias.numel() == CO);
+  const int rc = geops_conv5_pool_nwg_nhwc(
+      (const unsigned short*)in.data_ptr(),
+      (const unsigned short*)w_frags.data_ptr(),
+      has_bias ? bias.data_ptr<float>() : nullptr,
+      (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(), (int)N,
+      (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CI, (int)CO, (int)n_wg,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_pool_nwg_nhwc: unsupported geometry CI=", CI,
+              " CO=", CO);
+  launch_check("conv5_pool_nwg_nhwc");
 }
 
 void conv5_wrw_nhwc(torch::Tensor in, torch::Tensor gout, torch::Tensor part,
@@ -795,6 +837,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_direct_nhwc", &conv5_direct_nhwc);
   m.def("conv5_dgrad_nwg_nhwc", &conv5_dgrad_nwg_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
+  m.def("conv5_pool_nwg_nhwc", &conv5_pool_nwg_nhwc);
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
   m.def("fc_flatten_nchw", &fc_flatten_nchw);
