@@ -1179,6 +1179,37 @@ __global__ void k_pad_ch3to4_nhwc(const TIN* __restrict__ in,
   }
 }
 
+// Weight packing: the OIHW fp32 weight to per-lane MFMA B-fragment order
+// in bf16, out[i] = idx[i] == numel ? 0 : bf16(w[idx[i]]) (round to
+// nearest even, as Tensor.to(bfloat16) for finite values), for up to two
+// gather tables (ops/conv.py _frag_index) in one launch: the forward
+// and the data-gradient fragments of a layer come from one read of its
+// weight. One thread per 8 elements (a fragment lane's 16 B); an index
+// outside [0, numel) reads nothing and gives zero.
+__global__ __launch_bounds__(256) void k_conv5_pack_frags(
+    const float* __restrict__ w, long long numel,
+    const long long* __restrict__ idx0, bf16_t* __restrict__ out0,
+    long long n0, const long long* __restrict__ idx1,
+    bf16_t* __restrict__ out1, long long n1) {
+  long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long* idx = idx0;
+  bf16_t* out = out0;
+  if (g >= n0 / 8) {
+    g -= n0 / 8;
+    if (g >= n1 / 8) return;
+    idx = idx1;
+    out = out1;
+  }
+  __attribute__((aligned(16))) bf16_t v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const long long e = idx[g * 8 + j];
+    v[j] = (unsigned long long)e < (unsigned long long)numel ? cf2bf(w[e])
+                                                             : (bf16_t)0;
+  }
+  *reinterpret_cast<uint4*>(out + g * 8) = *reinterpret_cast<uint4*>(v);
+}
+
 static inline int conv_blocks(long long rows) {
   long long blocks = (rows + 3) / 4;  // 4 waves per block, 1 row per wave
   if (blocks < 1) blocks = 1;
@@ -1381,6 +1412,20 @@ int geops_conv5_pool_nwg_nhwc(const bf16_t* in, const bf16_t* w_frags,
   if (n_wg < 1) return -1;
   return conv5_pool_launch(in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo,
                            CI, CO, n_wg, s);
+}
+
+// n0, n1: element counts of the two tables, multiples of 8; n1 == 0 (and
+// null idx1/out1) packs one table.
+int geops_conv5_pack_frags(const float* w, long long numel,
+                           const long long* idx0, bf16_t* out0, long long n0,
+                           const long long* idx1, bf16_t* out1, long long n1,
+                           hipStream_t s) {
+  if (n0 <= 0 || n1 < 0 || (n0 & 7) || (n1 & 7)) return -1;
+  const long long blocks = ((n0 + n1) / 8 + 255) / 256;
+  if (blocks > 0x7fffffffLL) return -1;
+  hipLaunchKernelGGL(k_conv5_pack_frags, dim3((int)blocks), dim3(256), 0, s,
+                     w, numel, idx0, out0, n0, idx1, out1, n1);
+  return 0;
 }
 
 void geops_pad_ch3to4_nhwc(const void* in, bf16_t* out, long long npix,

@@ -30,9 +30,15 @@
 // rows; 4 waves split the 25 (kh,kw) tap tiles round-robin and each
 // wave computes BOTH o-tiles for its taps (A-fragment reuse), keeping
 // all accumulators in VGPRs until one final per-workgroup slab flush
-// (partials summed in torch). The CI=4 kernel (conv1) packs its taps
-// differently and pipelines its reads and its staging; it is described
-// at k_conv5_wrw4_nhwc below.
+// (partials summed in torch). Fragment reads are compiler-counted
+// builtins issued a few tap tiles ahead of their MFMAs, across (row,
+// window) steps; the bias tile reads a constant LDS image of ones; the
+// pooled form fetches the next block's gradient and codes during the
+// MFMA phase; the launcher picks a straight-line walk (STRAIGHT) where
+// every block is full-width and two rows high. Every slab row is
+// written, so the caller need not clear the slabs. The CI=4 kernel
+// (conv1) packs its taps differently and double-buffers its A image; it
+// is described at k_conv5_wrw4_nhwc below.
 
 #include <hip/hip_runtime.h>
 
@@ -67,7 +73,20 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
                                void*)p;
 }
 
-template <int COT, int PIX, bool UNPOOL = false>
+// The same read as a builtin: its result lands in MFMA operand registers
+// without a repack and the compiler counts its lgkmcnt wait, so reads can
+// stay in flight across MFMAs (both wrw kernels pipeline them this way).
+__device__ __forceinline__ bf16x4 tr16_ld(
+    const __attribute__((address_space(3))) char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) bf16x4*)p);
+}
+
+// STRAIGHT: every block is a full-width two-row block (Wo > 32 * (WMAX -
+// 1), Ho even), the launcher's choice; the walk is then straight-line
+// code. A kernel holds ONE form of the walk: with both behind a branch
+// the accumulators get two register sets and copies between them.
+template <int COT, int PIX, bool UNPOOL = false, bool STRAIGHT = false>
 __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
     const bf16_t* __restrict__ in,    // [N][Hi][Wi][16]
     const bf16_t* __restrict__ gout,  // [N][Ho][Wo][CO]; UNPOOL: the
@@ -89,13 +108,23 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
   constexpr int RPB = NCH * 1024;                      // region bytes
   constexpr int NROW_IN = WRW2_R + 4;
   constexpr int NROW_GO = WRW2_R * COT;
+  // a gout row holds the WMAX * 32 pixels the K windows read, so the
+  // last 1 KiB of its region is free; that of the last region holds the
+  // bias tile's A image, 4 pixel rows of [1.0, 0 x 15] at +0 (k-pixels
+  // 0..15) and at +512 (k-pixels 16..31)
+  constexpr int WMAX = (PIX - 4) / 32;   // K windows of a full row
+  constexpr int ONES = (NROW_IN + NROW_GO) * RPB - 1024;
+  constexpr int ONES_BYTES = 512 + 128;
+  static_assert(WMAX * 1024 + 1024 <= RPB, "room for the ones image");
   __shared__ __attribute__((aligned(128))) char lds_all[(NROW_IN + NROW_GO) *
                                                         RPB];
+
+  typedef const __attribute__((address_space(3))) char* lds_cptr;
 
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4;
   const int m = lane & 15;
-  const int wid = threadIdx.x >> 6;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   const int W = (Wo + 31) >> 5;          // 32-pixel K windows per row
   const int blocks_h = (Ho + WRW2_R - 1) / WRW2_R;
@@ -103,9 +132,16 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
 
-  const unsigned lds0 = lds_addr(lds_all);
+  const lds_cptr lds3 = (lds_cptr)lds_all;
 
-  // wave-owned tap tiles: tt = wid + 4*j, accumulators for BOTH o-tiles
+  // wave-owned tap tiles: tt = wid + 4*j, accumulators for BOTH o-tiles.
+  // Wave 0 owns 7 taps, waves 1..3 own 6. Slot j = 6 of wave 1 (tt = 25)
+  // is the bias tile: its A fragment, row 0 all ones and rows 1..15 zero
+  // (D[0][o] = sum_k B[k][o]), is read from the ONES image like any tap,
+  // at a fixed address. Waves 2 and 3 run the same slot into accumulators
+  // that are never flushed: with the slot behind a wave-dependent branch
+  // the compiler splits the accumulators over two register sets (112
+  // AGPRs, copies in the walk, 2 workgroups per CU).
   constexpr int MAXT = (NT + 3) / 4;     // 7
   f32x4 acc[MAXT][COT];
 #pragma unroll
@@ -113,192 +149,255 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
 #pragma unroll
     for (int t = 0; t < COT; ++t) acc[j][t] = (f32x4)0.0f;
 
-  for (long long blk = wg; blk < n_blocks; blk += n_wg) {
-    const int bh = (int)(blk % blocks_h);
-    const long long n = blk / blocks_h;
+  // per-lane fragment bases at (gout row 0, window 0): step (r, w) is a
+  // constant offset from them, except for slot 6 of waves 1..3, which
+  // stays on the ONES image (step6 = 0)
+  lds_cptr ab[MAXT];
+#pragma unroll
+  for (int j = 0; j < MAXT; ++j) {
+    const int tt = wid + 4 * j;
+    const int kh = tt / 5;
+    const int kw = tt - kh * 5;
+    ab[j] = tt < NT ? lds3 + kh * RPB + (kw + 4 * q) * 32 + m * 8
+                    : lds3 + ONES + m * 8;
+  }
+  const int step6 = wid == 0 ? 1 : 0;
+  const lds_cptr bb = lds3 + NROW_IN * RPB + (4 * q) * 32 + m * 8;
+  if (threadIdx.x < ONES_BYTES / 16)     // visible after the first barrier
+    reinterpret_cast<uint4*>(lds_all + ONES)[threadIdx.x] =
+        make_uint4((threadIdx.x & 1) ? 0u : 0x3F80u, 0u, 0u, 0u);
+
+  // ---- staging pieces, chunks round-robin over the 4 waves.
+  // A rows by LDS-DMA: a global NHWC row IS the LDS [pix][16] row.
+  auto stage_a = [&](long long n, int bh) {
     const int ho0 = bh * WRW2_R;
     const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
-    const int irows = nrows + 4;
-
-    // ---- stage via LDS-DMA: chunks round-robin over the 4 waves.
-    // A rows: a global NHWC row IS the LDS [pix][16] row (straight copy).
-    {
-      const int nchunks_a = irows * NCH;
-      for (int t = wid; t < nchunks_a; t += 4) {
-        const int ir = t / NCH;
-        const int c = t - ir * NCH;
-        const int slot = c * 64 + lane;              // 16B granule index
-        const int pix = slot >> 1;
-        const bf16_t* src =
-            (pix < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                               (long long)slot * 8)
-                       : g_wrw2_zeros;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)src,
-            (__attribute__((address_space(3))) void*)(lds_all + ir * RPB +
-                                                      c * 1024),
-            16, 0, 0);
-      }
-      if constexpr (UNPOOL) {
-        // gout rows from the POOLED gradient + argmax mask (Ho, Wo
-        // even, so the block's 2 rows are pooled row bh): item `it` is
-        // one 16 B granule (8 channels) of pooled pixel wp, contiguous
-        // in global memory, and expands to its 4 full-resolution
-        // positions. Items past the row (wp >= Wo/2) write the zero
-        // tail [Wo, 32*W) the K windows read. Loads first, then the
-        // selects and ds_writes.
-        constexpr int GV = CO / 8;
-        constexpr int WMAX = (PIX - 4) / 32;
-        constexpr int NIT = (16 * WMAX * GV + WRW2_THREADS - 1) /
-                            WRW2_THREADS;
-        const int nit = 16 * W * GV;
-        const int nreal = (Wo >> 1) * GV;
-        const long long rowv =
-            (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * GV;
-        uint4 gq[NIT];
-        uint2 mq[NIT];
+    const int nchunks_a = (nrows + 4) * NCH;
+    for (int t = wid; t < nchunks_a; t += 4) {
+      const int ir = t / NCH;
+      const int c = t - ir * NCH;
+      const int slot = c * 64 + lane;              // 16B granule index
+      const int pix = slot >> 1;
+      const bf16_t* src =
+          (pix < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
+                             (long long)slot * 8)
+                     : g_wrw2_zeros;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(lds_all + ir * RPB +
+                                                    c * 1024),
+          16, 0, 0);
+    }
+  };
+  // gout rows (full-resolution form): global [pix][CO] -> per-o-tile LDS
+  // [pix][16], by LDS-DMA
+  auto stage_b = [&](long long n, int bh) {
+    const int ho0 = bh * WRW2_R;
+    const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
+    const int nchunks_b = nrows * COT * WMAX;
+    for (int t = wid; t < nchunks_b; t += 4) {
+      const int rr = t / (COT * WMAX);
+      const int rem = t - rr * (COT * WMAX);
+      const int ot = rem / WMAX;
+      const int c = rem - ot * WMAX;
+      const int slot = c * 64 + lane;
+      const int pix = slot >> 1;
+      const int half = slot & 1;
+      const bf16_t* src =
+          (pix < Wo)
+              ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
+                        (long long)pix * CO + ot * 16 + half * 8)
+              : g_wrw2_zeros;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(lds_all +
+                                                    (NROW_IN + rr * COT +
+                                                     ot) * RPB +
+                                                    c * 1024),
+          16, 0, 0);
+    }
+  };
+  // UNPOOL: gout rows from the POOLED gradient + argmax mask (Ho, Wo
+  // even, so a block's 2 rows are pooled row bh): item `it` is one 16 B
+  // granule (8 channels) of pooled pixel wp, contiguous in global
+  // memory, and expands to its 4 full-resolution positions. Items past
+  // the row (wp >= Wo/2) write the zero tail [Wo, 32*W) the K windows
+  // read. The loads of the NEXT block wait in registers through this
+  // block's MFMA phase; the selects and ds_writes run after it.
+  constexpr int GV = CO / 8;
+  constexpr int NIT = (16 * WMAX * GV + WRW2_THREADS - 1) / WRW2_THREADS;
+  uint4 gq[NIT];
+  uint2 mq[NIT];
+  auto load_pooled = [&](long long n, int bh) {
+    const int nreal = (Wo >> 1) * GV;
+    const long long rowv = (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * GV;
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-          const int it = threadIdx.x + i * WRW2_THREADS;
-          gq[i] = make_uint4(0u, 0u, 0u, 0u);
-          mq[i] = make_uint2(~0u, ~0u);
-          if (it < nreal) {
-            gq[i] = reinterpret_cast<const uint4*>(gout)[rowv + it];
-            mq[i] = reinterpret_cast<const uint2*>(mask)[rowv + it];
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-          const int it = threadIdx.x + i * WRW2_THREADS;
-          if (it < nit) {
-            const int wp = it / GV;
-            const int rem = it - wp * GV;
-            const int ot = rem >> 1;
-            const int half = rem & 1;
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-              for (int dx = 0; dx < 2; ++dx)
-                *reinterpret_cast<uint4*>(
-                    lds_all + (NROW_IN + dy * COT + ot) * RPB +
-                    (2 * wp + dx) * 32 + half * 16) =
-                    unpool_select(gq[i], mq[i], dy * 2 + dx);
-          }
-        }
-      }
-      // gout rows: global [pix][CO] -> per-o-tile LDS [pix][16]
-      const int nchunks_b = UNPOOL ? 0 : nrows * COT * NCH;
-      for (int t = wid; t < nchunks_b; t += 4) {
-        const int rr = t / (COT * NCH);
-        const int rem = t - rr * (COT * NCH);
-        const int ot = rem / NCH;
-        const int c = rem - ot * NCH;
-        const int slot = c * 64 + lane;
-        const int pix = slot >> 1;
-        const int half = slot & 1;
-        const bf16_t* src =
-            (pix < Wo)
-                ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
-                          (long long)pix * CO + ot * 16 + half * 8)
-                : g_wrw2_zeros;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)src,
-            (__attribute__((address_space(3))) void*)(lds_all +
-                                                      (NROW_IN + rr * COT +
-                                                       ot) * RPB +
-                                                      c * 1024),
-            16, 0, 0);
+    for (int i = 0; i < NIT; ++i) {
+      const int it = threadIdx.x + i * WRW2_THREADS;
+      gq[i] = make_uint4(0u, 0u, 0u, 0u);
+      mq[i] = make_uint2(~0u, ~0u);
+      if (it < nreal) {
+        gq[i] = reinterpret_cast<const uint4*>(gout)[rowv + it];
+        mq[i] = reinterpret_cast<const uint2*>(mask)[rowv + it];
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
+  auto write_pooled = [&]() {
+    const int nit = 16 * W * GV;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      const int it = threadIdx.x + i * WRW2_THREADS;
+      if (it < nit) {
+        const int wp = it / GV;
+        const int rem = it - wp * GV;
+        const int ot = rem >> 1;
+        const int half = rem & 1;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 2; ++dx)
+            *reinterpret_cast<uint4*>(
+                lds_all + (NROW_IN + dy * COT + ot) * RPB +
+                (2 * wp + dx) * 32 + half * 16) =
+                unpool_select(gq[i], mq[i], dy * 2 + dx);
+      }
+    }
+  };
+
+  // ---- the (row, window) walk of one block. Fragment reads are
+  // compiler-counted builtins, issued DEPTH tap tiles ahead of the MFMAs
+  // that use them, across step boundaries: tile j of a step lives in
+  // afr[j], which is free for the next step's tile j once this step's
+  // MFMA j is issued. The window's B fragments are held in `bcur` for
+  // the whole step; the next step's arrive in `bnxt` ahead of its first
+  // tile. The walk has no wave-dependent branch (slot 6 differs between
+  // the waves by its address alone), so it is straight-line code.
+  // Every accumulator still receives its MFMAs in (row, window) order;
+  // only the interleaving of different accumulators with the reads
+  // changed. The sched_barriers pin that program order; the compiler
+  // places the counted lgkmcnt waits.
+  constexpr int DEPTH = 3;
+  static_assert(DEPTH < MAXT, "a slot is refilled after its MFMA");
+  bf16x4 afr[MAXT][2];
+  bf16x4 bcur[COT][2], bnxt[COT][2];
+  auto ld_a = [&](int j, int oa) __attribute__((always_inline)) {
+    const lds_cptr p = j < MAXT - 1 ? ab[j] + oa : ab[j] + oa * step6;
+    afr[j][0] = tr16_ld(p);
+    afr[j][1] = tr16_ld(p + 512);            // k-pixels 16..31
+  };
+  auto ld_b = [&](bf16x4 (&b)[COT][2], int ob) __attribute__((always_inline)) {
+#pragma unroll
+    for (int ot = 0; ot < COT; ++ot) {
+      b[ot][0] = tr16_ld(bb + ob + ot * RPB);
+      b[ot][1] = tr16_ld(bb + ob + ot * RPB + 512);
+    }
+  };
+  auto mma = [&](int j) __attribute__((always_inline)) {
+    union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
+    a.p.lo = afr[j][0];
+    a.p.hi = afr[j][1];
+#pragma unroll
+    for (int ot = 0; ot < COT; ++ot) {
+      union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
+      b.p.lo = bcur[ot][0];
+      b.p.hi = bcur[ot][1];
+      acc[j][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          a.v, b.v, acc[j][ot], 0, 0, 0);
+    }
+  };
+  // one step at offsets (oa, ob); (oa_n, ob_n) is the step after it
+  auto step = [&](int oa, int ob, int oa_n, int ob_n, bool has_next)
+                  __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+      const int jn = j + DEPTH;
+      if (jn < MAXT) {
+        ld_a(jn, oa);
+      } else if (has_next) {
+        if (jn == MAXT) ld_b(bnxt, ob_n);
+        ld_a(jn - MAXT, oa_n);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      mma(j);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (has_next) {
+#pragma unroll
+      for (int ot = 0; ot < COT; ++ot) {
+        bcur[ot][0] = bnxt[ot][0];
+        bcur[ot][1] = bnxt[ot][1];
+      }
+    }
+  };
+  // (row r, window w) -> byte offsets in the A and the gout image
+  auto off_a = [&](int r, int w) { return r * RPB + w * 1024; };
+  auto off_b = [&](int r, int w) { return r * COT * RPB + w * 1024; };
+  auto walk = [&](int nrows) __attribute__((always_inline)) {
+    ld_b(bcur, 0);
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) ld_a(j, 0);
+    if constexpr (STRAIGHT) {
+      // full-width two-row blocks (the flagship): every offset is an
+      // immediate, the walk is straight-line code
+      constexpr int NS = WRW2_R * WMAX;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int s1 = s + 1 < NS ? s + 1 : s;
+        step(off_a(s / WMAX, s % WMAX), off_b(s / WMAX, s % WMAX),
+             off_a(s1 / WMAX, s1 % WMAX), off_b(s1 / WMAX, s1 % WMAX),
+             s + 1 < NS);
+      }
+    } else {
+      // any other width, and one-row tail blocks: the same pipeline in a
+      // loop. The step after the last re-reads the last one (in bounds,
+      // unused), so a trip has no branch of its own.
+      const int nsteps = nrows * W;
+      int r = 0, w = 0;
+      for (int s = 0; s < nsteps; ++s) {
+        int rn = r, wn = w;
+        if (s + 1 < nsteps) {
+          wn = w + 1;
+          if (wn == W) { wn = 0; rn = r + 1; }
+        }
+        step(off_a(r, w), off_b(r, w), off_a(rn, wn), off_b(rn, wn), true);
+        r = rn;
+        w = wn;
+      }
+    }
+  };
+
+  // block = (image n, row pair bh), decoded once, one block ahead
+  long long blk = wg;
+  long long n = 0;
+  int bh = 0;
+  if (blk < n_blocks) {
+    n = blk / blocks_h;
+    bh = (int)(blk - n * blocks_h);
+    if constexpr (UNPOOL) load_pooled(n, bh);
+  }
+  for (; blk < n_blocks; blk += n_wg) {
+    const int ho0 = bh * WRW2_R;
+    const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
+
+    // ---- stage this block's images
+    stage_a(n, bh);
+    if constexpr (UNPOOL) {
+      write_pooled();
+    } else {
+      stage_b(n, bh);
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the LDS-DMA pieces
     __syncthreads();
 
-    for (int r = 0; r < nrows; ++r) {
-      // A-row base addresses for this wave's 7 tap tiles (tt clamped so
-      // the unused 7th tile of waves 1-3 still reads in-bounds LDS; its
-      // MFMA is skipped)
-      unsigned abase[MAXT];
-#pragma unroll
-      for (int j = 0; j < MAXT; ++j) {
-        int tt = wid + 4 * j;
-        if (tt >= NT) tt = NT - 1;
-        const int kh = tt / 5;
-        const int kw = tt - kh * 5;
-        abase[j] = lds0 + (r + kh) * RPB + (kw + 4 * q) * 32 + m * 8;
-      }
-      const unsigned bbase0 = lds0 + (NROW_IN + r * COT + 0) * RPB +
-                              (4 * q) * 32 + m * 8;
-      const unsigned bbase1 = lds0 + (NROW_IN + r * COT + (COT - 1)) * RPB +
-                              (4 * q) * 32 + m * 8;
-      for (int w = 0; w < W; ++w) {
-        const unsigned poff = (unsigned)(w * 32 * 32);  // pix0 bytes
-        // ONE asm block issues every tr read for this (r,w) and ends
-        // with the lgkmcnt drain: the compiler materialises the
-        // bf16x4->bf16x8 repack VALU at an asm OUTPUT's def site, so
-        // any multi-asm structure lets it consume un-landed tr
-        // destinations BEFORE a separate wait (observed: v_lshrrev/
-        // v_perm ahead of s_waitcnt -> corrupt fragments). Outputs are
-        // early-clobber so no read's destination aliases a later-used
-        // address register.
-        bf16x4 bfr[2][2];
-        bf16x4 afr[MAXT][2];
-        asm volatile(
-            "ds_read_b64_tr_b16 %0, %18\n\t"
-            "ds_read_b64_tr_b16 %1, %18 offset:512\n\t"
-            "ds_read_b64_tr_b16 %2, %19\n\t"
-            "ds_read_b64_tr_b16 %3, %19 offset:512\n\t"
-            "ds_read_b64_tr_b16 %4, %20\n\t"
-            "ds_read_b64_tr_b16 %5, %20 offset:512\n\t"
-            "ds_read_b64_tr_b16 %6, %21\n\t"
-            "ds_read_b64_tr_b16 %7, %21 offset:512\n\t"
-            "ds_read_b64_tr_b16 %8, %22\n\t"
-            "ds_read_b64_tr_b16 %9, %22 offset:512\n\t"
-            "ds_read_b64_tr_b16 %10, %23\n\t"
-            "ds_read_b64_tr_b16 %11, %23 offset:512\n\t"
-            "ds_read_b64_tr_b16 %12, %24\n\t"
-            "ds_read_b64_tr_b16 %13, %24 offset:512\n\t"
-            "ds_read_b64_tr_b16 %14, %25\n\t"
-            "ds_read_b64_tr_b16 %15, %25 offset:512\n\t"
-            "ds_read_b64_tr_b16 %16, %26\n\t"
-            "ds_read_b64_tr_b16 %17, %26 offset:512\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(bfr[0][0]), "=&v"(bfr[0][1]), "=&v"(bfr[1][0]),
-              "=&v"(bfr[1][1]), "=&v"(afr[0][0]), "=&v"(afr[0][1]),
-              "=&v"(afr[1][0]), "=&v"(afr[1][1]), "=&v"(afr[2][0]),
-              "=&v"(afr[2][1]), "=&v"(afr[3][0]), "=&v"(afr[3][1]),
-              "=&v"(afr[4][0]), "=&v"(afr[4][1]), "=&v"(afr[5][0]),
-              "=&v"(afr[5][1]), "=&v"(afr[6][0]), "=&v"(afr[6][1])
-            : "v"(bbase0 + poff), "v"(bbase1 + poff),
-              "v"(abase[0] + poff), "v"(abase[1] + poff),
-              "v"(abase[2] + poff), "v"(abase[3] + poff),
-              "v"(abase[4] + poff), "v"(abase[5] + poff),
-              "v"(abase[6] + poff)
-            : "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < MAXT; ++j) {
-          const int tt = wid + 4 * j;
-          const bool bias_tile = (tt == NT);   // spare slot: wid 1, j 6
-          if (tt >= NT && !bias_tile) continue;
-          union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
-          if (bias_tile) {
-            const bf16x8 ones = (bf16x8)(short)0x3F80;  // bf16 1.0 splat
-            a.v = (m == 0) ? ones : (bf16x8)(short)0;
-          } else {
-            a.p.lo = afr[j][0];
-            a.p.hi = afr[j][1];
-          }
-#pragma unroll
-          for (int ot = 0; ot < COT; ++ot) {
-            union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
-            b.p.lo = bfr[ot][0];
-            b.p.hi = bfr[ot][1];
-            acc[j][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a.v, b.v, acc[j][ot], 0, 0, 0);
-          }
-        }
-      }
+    // ---- the next block's pooled gradient and codes fly during this
+    // block's MFMA phase
+    if (blk + n_wg < n_blocks) {
+      n = (blk + n_wg) / blocks_h;
+      bh = (int)(blk + n_wg - n * blocks_h);
+      if constexpr (UNPOOL) load_pooled(n, bh);
     }
+
+    walk(nrows);
     __syncthreads();  // before the next block restages LDS
   }
 
@@ -375,8 +474,8 @@ __global__ void k_tr16_probe(const bf16_t* __restrict__ in,
 // MFMAs, so each (tap, o) and bias sum is the sum the 10-tile kernel
 // (tiles t = kw*2 + kh/4, before) computed, bit for bit; the flush
 // scatters the live rows to that kernel's slab rows
-// (kw*2 + kh/4)*16 + (kh%4)*4 + ci, bias in row 160, and leaves the
-// other rows as the caller zeroed them.
+// (kw*2 + kh/4)*16 + (kh%4)*4 + ci, bias in row 160, and writes zeros
+// to the other rows.
 //
 // Schedule: fragment reads are compiler-counted builtins
 // (__builtin_amdgcn_ds_read_tr16_b64_v4i16), software-pipelined two
@@ -394,12 +493,6 @@ __global__ void k_tr16_probe(const bf16_t* __restrict__ in,
 // barrier that ends it. The full-resolution form stages gout by LDS-DMA
 // into its single image between the two barriers.
 // ---------------------------------------------------------------------
-
-__device__ __forceinline__ bf16x4 tr16_ld(
-    const __attribute__((address_space(3))) char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) bf16x4*)p);
-}
 
 // One 1 KiB LDS-DMA piece (16 B per lane) that the compiler does not
 // see: for a __builtin_amdgcn_global_load_lds in flight hipcc puts
@@ -682,7 +775,8 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
   }
 
   // ---- flush the live D rows (row = q*4 + i, col = m = o) to the slab
-  // rows of the 10-tile layout; everything else stays as zeroed
+  // rows of the 10-tile layout; the dead rows get zeros below, so the
+  // caller need not clear the slab
   float* base = part + (long long)wg * T16 * CO;
 #pragma unroll
   for (int j = 0; j < TPW; ++j) {
@@ -699,6 +793,20 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
         slot = q == 0 ? 9 * 16 + i : ((q == 1 && i == 0) ? 160 : -1);
       if (slot >= 0) base[(long long)slot * CO + m] = acc[j][i];
     }
+  }
+  // the dead rows: 4..15 of the five kh = 4 tiles (12 rows = 48 float4
+  // each) and the 15 rows behind the bias row (60 float4)
+  static_assert(WRW2_THREADS >= 5 * 48, "");
+  {
+    const int t = threadIdx.x;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < 5 * 48) {
+      const int kw = t / 48;
+      const int off = t - kw * 48;
+      reinterpret_cast<float4*>(base + ((2 * kw + 1) * 16 + 4) * CO)[off] = z;
+    }
+    if (t < 15 * CO / 4)
+      reinterpret_cast<float4*>(base + 161 * CO)[t] = z;
   }
 }
 
@@ -735,21 +843,29 @@ static int wrw16_launch(const bf16_t* in, const bf16_t* gout,
   if (mask && ((Ho | Wo) & 1)) return -1;
   const int W = (Wo + 31) >> 5;
   const int need = (W * 32 + 4) > Wi ? (W * 32 + 4) : Wi;
+#define W2KERNEL(COT_, PIX_, UNPOOL_, STRAIGHT_)                          \
+  hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, UNPOOL_, STRAIGHT_>), \
+                     dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout, part, \
+                     Nn, Hi, Wi, Ho, Wo, mask)
+  // straight-line walk: every row has the variant's full window count
+  // and no block is a one-row tail
 #define W2LAUNCH(COT_, PIX_)                                              \
   if (need <= PIX_) {                                                     \
-    if (mask)                                                             \
-      hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, true>),          \
-                         dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout,  \
-                         part, Nn, Hi, Wi, Ho, Wo, mask);                 \
+    const bool straight = W == (PIX_ - 4) / 32 && !(Ho & 1);              \
+    if (mask && straight)                                                 \
+      W2KERNEL(COT_, PIX_, true, true);                                   \
+    else if (mask)                                                        \
+      W2KERNEL(COT_, PIX_, true, false);                                  \
+    else if (straight)                                                    \
+      W2KERNEL(COT_, PIX_, false, true);                                  \
     else                                                                  \
-      hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, false>),         \
-                         dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout,  \
-                         part, Nn, Hi, Wi, Ho, Wo, mask);                 \
+      W2KERNEL(COT_, PIX_, false, false);                                 \
     return n_wg;                                                          \
   }
   if (CO == 32) { W2LAUNCH(2, 136) W2LAUNCH(2, 232) }
   if (CO == 16) { W2LAUNCH(1, 136) W2LAUNCH(1, 232) }
 #undef W2LAUNCH
+#undef W2KERNEL
   return -1;
 }
 

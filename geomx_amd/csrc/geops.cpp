@@ -89,6 +89,9 @@ int geops_conv5_pool_nwg_nhwc(const unsigned short*, const unsigned short*,
                               int, int, int, int, int, int, int, hipStream_t);
 void geops_pad_ch3to4_nhwc(const void*, unsigned short*, long long, int,
                            hipStream_t);
+int geops_conv5_pack_frags(const float*, long long, const long long*,
+                           unsigned short*, long long, const long long*,
+                           unsigned short*, long long, hipStream_t);
 int geops_conv5_wrw16_nhwc(const unsigned short*, const unsigned short*,
                            float*, int, int, int, int, int, int, int, int,
                            hipStream_t);
@@ -612,6 +615,42 @@ void pad_ch3to4_nhwc(torch::Tensor in, torch::Tensor out, int64_t npix) {
   launch_check("pad_ch3to4_nhwc");
 }
 
+// Pack an fp32 conv weight into bf16 MFMA fragment order through one or
+// two gather tables of ops/conv.py (index == weight.numel() means zero)
+// in one launch; returns one packed tensor per table.
+std::vector<torch::Tensor> conv5_pack_frags(torch::Tensor weight,
+                                            torch::Tensor idx0,
+                                            c10::optional<torch::Tensor> idx1) {
+  TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() &&
+                  weight.scalar_type() == torch::kFloat32,
+              "conv5_pack_frags: weight must be contiguous fp32 on the GPU");
+  const bool two = idx1.has_value() && idx1->defined();
+  auto check_idx = [&](const torch::Tensor& t) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                    t.scalar_type() == torch::kInt64 &&
+                    t.device() == weight.device() && t.numel() > 0 &&
+                    t.numel() % 8 == 0,
+                "conv5_pack_frags: index tables are contiguous int64 on the "
+                "weight's device, a multiple of 8 long");
+  };
+  check_idx(idx0);
+  if (two) check_idx(*idx1);
+  const auto opts = weight.options().dtype(torch::kBFloat16);
+  std::vector<torch::Tensor> out;
+  out.push_back(torch::empty({idx0.numel()}, opts));
+  if (two) out.push_back(torch::empty({idx1->numel()}, opts));
+  const int rc = geops_conv5_pack_frags(
+      weight.data_ptr<float>(), (long long)weight.numel(),
+      (const long long*)idx0.data_ptr<int64_t>(),
+      (unsigned short*)out[0].data_ptr(), (long long)idx0.numel(),
+      two ? (const long long*)idx1->data_ptr<int64_t>() : nullptr,
+      two ? (unsigned short*)out[1].data_ptr() : nullptr,
+      two ? (long long)idx1->numel() : 0LL, cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_pack_frags: bad table sizes");
+  launch_check("conv5_pack_frags");
+  return out;
+}
+
 void sgd_update(torch::Tensor w, torch::Tensor g, double lr, double wd,
                 double rescale) {
   check_f32(w, "w"); check_f32(g, "g");
@@ -831,6 +870,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequantize_4bit", &dequantize_4bit);
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
+  m.def("conv5_pack_frags", &conv5_pack_frags, py::arg("weight"),
+        py::arg("idx0"), py::arg("idx1") = py::none());
   m.def("conv5_wrw_nhwc", &conv5_wrw_nhwc);
   m.def("conv5_wrw_unpool_nhwc", &conv5_wrw_unpool_nhwc);
   m.def("conv5_dgrad_unpool_nhwc", &conv5_dgrad_unpool_nhwc);

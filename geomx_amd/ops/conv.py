@@ -141,7 +141,9 @@ def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
     Ho, Wo = (Hi - 4, Wi - 4) if mask is not None else go.shape[2:]
     n_blocks = N * ((Ho + 3) // 4)
     n_wg = min(_WRW_NWG, n_blocks)
-    part = torch.zeros(n_wg, T16, CO, dtype=torch.float32,
+    # both kernels write every row of every slab (wrw4 zeroes its dead
+    # rows in the flush), so nothing has to be cleared first
+    part = torch.empty(n_wg, T16, CO, dtype=torch.float32,
                        device=go.device)
     if mask is not None:
         _geops.conv5_wrw_unpool_nhwc(xb_padded, go, mask, part, N, Hi, Wi,
@@ -271,6 +273,18 @@ def _w_frags(weight: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return wz[idx].contiguous()
 
 
+def _pack_frags(weight: torch.Tensor, *idx):
+    """Fragment-order bf16 copies of the weight for one or two gather
+    tables, as a list: one launch of k_conv5_pack_frags for an fp32
+    weight on the GPU, _w_frags per table on the CPU, without the
+    extension, or for another dtype (same values either way)."""
+    w = weight.detach()
+    if w.is_cuda and w.dtype == torch.float32 and native_available():
+        from geomx_amd import _geops
+        return _geops.conv5_pack_frags(w.contiguous(), *idx)
+    return [_w_frags(w, i) for i in idx]
+
+
 def _empty_nhwc(N, C, H, W, device) -> torch.Tensor:
     return torch.empty(N, C, H, W, dtype=torch.bfloat16, device=device,
                        memory_format=torch.channels_last)
@@ -310,9 +324,10 @@ def _pooled_backward(fuse: Conv5Unpool, need_x: bool, need_w: bool, gp,
     return grad_x, grad_wb
 
 
-def _dgrad(route, go, x_real, weight, idx, mask=None):
+def _dgrad(route, go, x_real, weight, idx, mask=None, w_frags=None):
     """grad_x of the conv from grad_out `go` (NHWC bf16); with `mask`
-    (route 'lds_pad4' only) `go` is the pooled gradient."""
+    (route 'lds_pad4' only) `go` is the pooled gradient. `w_frags`: the
+    dgrad fragments where the forward packed them already."""
     N, CIr, Hi, Wi = x_real.shape
     CO = go.shape[1]
     Ho, Wo = Hi - 4, Wi - 4
@@ -321,9 +336,10 @@ def _dgrad(route, go, x_real, weight, idx, mask=None):
         from geomx_amd import _geops
         COp = (CIr + 15) & ~15
         gx = _empty_nhwc(N, COp, Hi, Wi, go.device)
-        _geops.conv5_dgrad_unpool_nhwc(go, mask, _w_frags(weight, idx.dgrad),
-                                       gx, N, Ho + 8, Wo + 8, Hi, Wi, CO,
-                                       COp)
+        if w_frags is None:
+            w_frags, = _pack_frags(weight, idx.dgrad)
+        _geops.conv5_dgrad_unpool_nhwc(go, mask, w_frags, gx, N, Ho + 8,
+                                       Wo + 8, Hi, Wi, CO, COp)
         return gx[:, :CIr] if COp != CIr else gx
     if route == "aten":
         return torch.ops.aten.convolution_backward(
@@ -331,7 +347,8 @@ def _dgrad(route, go, x_real, weight, idx, mask=None):
             [0, 0], [1, 1], False, [0, 0], 1, [True, False, False])[0]
     from geomx_amd import _geops
     COp = (CIr + 15) & ~15
-    w_frags = _w_frags(weight, idx.dgrad)
+    if w_frags is None:
+        w_frags, = _pack_frags(weight, idx.dgrad)
     pad = 4
     if route == "direct_padded":
         # physical zero border: the direct kernel is interior-only (an
@@ -392,7 +409,7 @@ class _Conv5Fn(torch.autograd.Function):
             xb = x.to(torch.bfloat16)
         else:
             xb = _nhwc_bf16(x)
-        mask = None
+        mask = w_dfrags = None
         if plan.fwd == "aten":
             args = [xb[:, :CIr], weight.detach().to(torch.bfloat16),
                     None if bias is None else bias.detach().to(torch.bfloat16)]
@@ -404,7 +421,12 @@ class _Conv5Fn(torch.autograd.Function):
                 out = F.conv2d(*args)
         else:
             from geomx_amd import _geops
-            w_frags = _w_frags(weight, idx.fwd)
+            # one launch packs the forward fragments and, where backward
+            # will run a native data gradient, its fragments too
+            if plan.dgrad != "aten" and ctx.needs_input_grad[0]:
+                w_frags, w_dfrags = _pack_frags(weight, idx.fwd, idx.dgrad)
+            else:
+                w_frags, = _pack_frags(weight, idx.fwd)
             b = bias.detach().float() if bias is not None else torch.Tensor()
             if plan.fwd == "pool":
                 out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
@@ -418,7 +440,10 @@ class _Conv5Fn(torch.autograd.Function):
                                   xb.shape[1], CO, 0)
         # xb keeps its padded channels: the custom wrw wants CI % 4 == 0,
         # the ATen routes take the view xb[:, :CIr]
+        # the weight is saved too, so autograd's version check covers the
+        # dgrad fragments against an in-place change before backward
         ctx.save_for_backward(xb, weight, mask)
+        ctx.w_dfrags = w_dfrags
         ctx.plan, ctx.idx = plan, idx
         ctx.has_bias = bias is not None
         ctx.CIr = CIr
@@ -438,7 +463,8 @@ class _Conv5Fn(torch.autograd.Function):
                                              ctx.needs_input_grad[2])
 
         def dgrad(g, m):
-            return _dgrad(plan.dgrad, g, x_real, weight, idx, m)
+            return _dgrad(plan.dgrad, g, x_real, weight, idx, m,
+                          ctx.w_dfrags)
 
         def wrw(g, m):
             return _wrw(plan.wrw, g, xb, x_real, weight, idx, ctx.has_bias,
