@@ -31,8 +31,8 @@ void geops_bsc_pull_pack(const float*, float*, int*, long long*, long long,
 int geops_bsc_fused(const float*, float*, float*, float*, int*, const float*,
                     unsigned long long*, float, long long, long long, float,
                     hipStream_t);
-void geops_bsc_unpack(const float*, const int*, float*, long long, bool,
-                      hipStream_t);
+void geops_bsc_unpack(const float*, const int*, float*, long long, long long,
+                      bool, hipStream_t);
 void geops_dgt_contribution(const float*, float*, long long, int, int,
                             hipStream_t);
 void geops_quantize_4bit(const float*, float*, uint8_t*, float*, long long,
@@ -235,19 +235,22 @@ void bsc_unpack(torch::Tensor vals, torch::Tensor idx, torch::Tensor out,
                 bool accumulate) {
   check_f32(vals, "vals"); check_f32(out, "out");
   TORCH_CHECK(idx.scalar_type() == torch::kInt32 && idx.is_contiguous());
+  TORCH_CHECK(idx.is_cuda() && idx.numel() >= vals.numel(),
+              "idx must be a GPU tensor at least as long as vals");
   if (!accumulate) {
     hipMemsetAsync(out.data_ptr<float>(), 0, out.numel() * sizeof(float),
                    cur_stream());
   }
   geops_bsc_unpack(vals.data_ptr<float>(), idx.data_ptr<int32_t>(),
-                   out.data_ptr<float>(), vals.numel(), accumulate,
-                   cur_stream());
+                   out.data_ptr<float>(), vals.numel(), out.numel(),
+                   accumulate, cur_stream());
   launch_check("bsc_unpack");
 }
 
 void dgt_contribution(torch::Tensor g, torch::Tensor out, int64_t chunk) {
   check_f32(g, "g"); check_f32(out, "out");
   const long long n = g.numel();
+  TORCH_CHECK(chunk >= 1 && chunk <= INT32_MAX, "chunk must be positive");
   const int nchunks = (int)((n + chunk - 1) / chunk);
   TORCH_CHECK(out.numel() == nchunks);
   geops_dgt_contribution(g.data_ptr<float>(), out.data_ptr<float>(), n,

@@ -111,6 +111,17 @@ extern "C" __global__ void k_dequantize_2bit(const uint32_t* __restrict__ in,
 // Bi-Sparse: fused momentum correction (u = mu*u + g ; v += u)
 // ---------------------------------------------------------------------------
 
+// u*mu and + g are rounded SEPARATELY (no FMA contraction), exactly as
+// the golden model (two torch ops) and the sampled boundary prediction
+// do: the boundary is the |v| of one sampled element, so a fused
+// multiply-add that lands one ulp below it would drop that element, and
+// a mixed CPU/GPU party would drift apart in u and v.
+__device__ __forceinline__ float bsc_mom(float u, float mu, float g) {
+#pragma clang fp contract(off)
+  const float p = u * mu;
+  return p + g;
+}
+
 extern "C" __global__ void k_bsc_momentum(const float* __restrict__ g,
                                           float* __restrict__ u,
                                           float* __restrict__ v,
@@ -123,14 +134,14 @@ extern "C" __global__ void k_bsc_momentum(const float* __restrict__ g,
   float4* v4 = reinterpret_cast<float4*>(v);
   for (long long i = tid; i < n4; i += stride) {
     float4 gg = g4[i], uu = u4[i], vv = v4[i];
-    uu.x = uu.x * mu + gg.x; vv.x += uu.x;
-    uu.y = uu.y * mu + gg.y; vv.y += uu.y;
-    uu.z = uu.z * mu + gg.z; vv.z += uu.z;
-    uu.w = uu.w * mu + gg.w; vv.w += uu.w;
+    uu.x = bsc_mom(uu.x, mu, gg.x); vv.x += uu.x;
+    uu.y = bsc_mom(uu.y, mu, gg.y); vv.y += uu.y;
+    uu.z = bsc_mom(uu.z, mu, gg.z); vv.z += uu.z;
+    uu.w = bsc_mom(uu.w, mu, gg.w); vv.w += uu.w;
     u4[i] = uu; v4[i] = vv;
   }
   for (long long i = (n4 << 2) + tid; i < n; i += stride) {
-    float uu = u[i] * mu + g[i];
+    float uu = bsc_mom(u[i], mu, g[i]);
     u[i] = uu;
     v[i] += uu;
   }
@@ -347,14 +358,14 @@ extern "C" __global__ __launch_bounds__(GEOPS_THREADS, 4) void k_bsc_fused(
       float4 u1 = *reinterpret_cast<float4*>(u + i0 + 4);
       float4 v0 = *reinterpret_cast<float4*>(v + i0);
       float4 v1 = *reinterpret_cast<float4*>(v + i0 + 4);
-      u0.x = u0.x * mu + g0.x; v0.x += u0.x;
-      u0.y = u0.y * mu + g0.y; v0.y += u0.y;
-      u0.z = u0.z * mu + g0.z; v0.z += u0.z;
-      u0.w = u0.w * mu + g0.w; v0.w += u0.w;
-      u1.x = u1.x * mu + g1.x; v1.x += u1.x;
-      u1.y = u1.y * mu + g1.y; v1.y += u1.y;
-      u1.z = u1.z * mu + g1.z; v1.z += u1.z;
-      u1.w = u1.w * mu + g1.w; v1.w += u1.w;
+      u0.x = bsc_mom(u0.x, mu, g0.x); v0.x += u0.x;
+      u0.y = bsc_mom(u0.y, mu, g0.y); v0.y += u0.y;
+      u0.z = bsc_mom(u0.z, mu, g0.z); v0.z += u0.z;
+      u0.w = bsc_mom(u0.w, mu, g0.w); v0.w += u0.w;
+      u1.x = bsc_mom(u1.x, mu, g1.x); v1.x += u1.x;
+      u1.y = bsc_mom(u1.y, mu, g1.y); v1.y += u1.y;
+      u1.z = bsc_mom(u1.z, mu, g1.z); v1.z += u1.z;
+      u1.w = bsc_mom(u1.w, mu, g1.w); v1.w += u1.w;
       *reinterpret_cast<float4*>(u + i0) = u0;
       *reinterpret_cast<float4*>(u + i0 + 4) = u1;
       *reinterpret_cast<float4*>(v + i0) = v0;
@@ -371,7 +382,7 @@ extern "C" __global__ __launch_bounds__(GEOPS_THREADS, 4) void k_bsc_fused(
       for (int j = 0; j < 8; ++j) {
         const long long i = i0 + j;
         if (i < hi) {
-          const float uu = u[i] * mu + g[i];
+          const float uu = bsc_mom(u[i], mu, g[i]);
           u[i] = uu;
           const float vv = v[i] + uu;
           v[i] = vv;
@@ -476,12 +487,15 @@ extern "C" __global__ void k_bsc_fill_tail(float* __restrict__ vals,
 extern "C" __global__ void k_bsc_unpack(const float* __restrict__ vals,
                                         const int* __restrict__ idx,
                                         float* __restrict__ out,
-                                        long long k, bool accumulate) {
+                                        long long k, long long n,
+                                        bool accumulate) {
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = tid; i < k; i += stride) {
     const int j = idx[i];
-    if (j >= 0) {
+    // indices come off the wire: placeholders (-1) and anything outside
+    // [0, n) are skipped, as the row-sparse kernels skip out-of-range ids
+    if (j >= 0 && j < n) {
       if (accumulate)
         atomicAdd(out + j, vals[i]);
       else
@@ -503,7 +517,9 @@ extern "C" __global__ void k_dgt_contribution(const float* __restrict__ g,
     const long long lo = (long long)c * chunk;
     const long long hi = min(lo + chunk, n);
     float s = 0.0f;
-    const long long nvec = (hi - lo) >> 2;
+    // float4 loads need g + c*chunk 16-byte aligned: only when chunk is
+    // a multiple of 4 (g itself is); any other chunk takes the scalar loop
+    const long long nvec = ((chunk & 3) == 0) ? ((hi - lo) >> 2) : 0;
     const float4* g4 = reinterpret_cast<const float4*>(g + lo);
     for (long long q = threadIdx.x; q < nvec; q += blockDim.x) {
       const float4 v = g4[q];
@@ -594,7 +610,8 @@ extern "C" __global__ void k_quantize_4bit(const float* __restrict__ x,
   const float4* x4 = reinterpret_cast<const float4*>(x);
   float4* r4 = reinterpret_cast<float4*>(residual);
   for (long long q = tid; q < nq; q += stride) {
-    const int c = (int)((q << 2) >> log2c);  // chunk >= 64: one chunk per q
+    // chunk is a power of two >= 4: the 4 elements of q share one chunk
+    const int c = (int)((q << 2) >> log2c);
     const float lo = minmax[2 * c];
     const float step = fmaxf(minmax[2 * c + 1] - lo, 1e-30f) / 16.0f;
     const float inv = 1.0f / step;
@@ -1058,9 +1075,10 @@ void geops_bsc_pull_pack(const float* x, float* vals, int* idx,
 }
 
 void geops_bsc_unpack(const float* vals, const int* idx, float* out,
-                      long long k, bool accumulate, hipStream_t s) {
+                      long long k, long long n, bool accumulate,
+                      hipStream_t s) {
   hipLaunchKernelGGL(k_bsc_unpack, dim3(geops_blocks(k)),
-                     dim3(GEOPS_THREADS), 0, s, vals, idx, out, k,
+                     dim3(GEOPS_THREADS), 0, s, vals, idx, out, k, n,
                      accumulate);
 }
 

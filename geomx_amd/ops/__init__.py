@@ -49,6 +49,18 @@ def _on_gpu(*tensors) -> bool:
     return any(t.is_cuda for t in tensors if isinstance(t, torch.Tensor))
 
 
+def _flat_inplace(t: torch.Tensor, name: str) -> torch.Tensor:
+    """1-d VIEW of an operand a kernel writes. `.reshape(-1)` of a
+    non-contiguous tensor is a copy: the kernel would update the copy and
+    the caller's tensor would silently stay as it was. Such a tensor is an
+    error here, never a copy."""
+    if not t.is_contiguous():
+        raise ValueError(
+            "%s is updated in place by the kernel and must be contiguous "
+            "(shape %s, strides %s)" % (name, tuple(t.shape), t.stride()))
+    return t.view(-1)
+
+
 # ---------------------------------------------------------------------------
 # 2bit
 # ---------------------------------------------------------------------------
@@ -61,7 +73,8 @@ def quantize_2bit(grad: torch.Tensor, residual: torch.Tensor, threshold: float,
         g = _require_native()
         if out is None:
             out = torch.empty(nw, dtype=torch.int32, device=grad.device)
-        g.quantize_2bit(grad.reshape(-1), residual.reshape(-1), out, threshold)
+        g.quantize_2bit(grad.reshape(-1), _flat_inplace(residual, "residual"),
+                        _flat_inplace(out, "out"), threshold)
         return out
     packed = ref.quantize_2bit(grad, residual, threshold)
     if out is not None:
@@ -76,7 +89,7 @@ def dequantize_2bit(packed: torch.Tensor, n: int, threshold: float,
         g = _require_native()
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=packed.device)
-        g.dequantize_2bit(packed, out.reshape(-1), threshold)
+        g.dequantize_2bit(packed, _flat_inplace(out, "out"), threshold)
         return out
     return ref.dequantize_2bit(packed, n, threshold, out=out)
 
@@ -94,6 +107,7 @@ def bsc_compress(grad, u, v, ratio, momentum=ref.BSC_MOMENTUM, seed=42
         vals = torch.empty(k, dtype=torch.float32, device=grad.device)
         idx = torch.empty(k, dtype=torch.int32, device=grad.device)
         gflat = grad.reshape(-1)
+        u, v = _flat_inplace(u, "u"), _flat_inplace(v, "v")
         # boundary PREDICTED from the seeded sample of post-momentum v
         # (v + mu*u + g at the sample positions) as a DEVICE scalar, so
         # the fused kernel path never synchronizes with the host
@@ -178,9 +192,9 @@ def bsc_decompress(vals, idx, n, out=None, accumulate=False) -> torch.Tensor:
         g = _require_native()
         if out is None:
             out = torch.zeros(n, dtype=torch.float32, device=vals.device)
-            g.bsc_unpack(vals, idx, out.reshape(-1), True)
+            g.bsc_unpack(vals, idx, out, True)
             return out
-        g.bsc_unpack(vals, idx, out.reshape(-1), accumulate)
+        g.bsc_unpack(vals, idx, _flat_inplace(out, "out"), accumulate)
         return out
     return ref.bsc_decompress(vals, idx, n, out=out, accumulate=accumulate)
 
@@ -209,7 +223,8 @@ def quantize_4bit_chunked(x: torch.Tensor, chunk_elems: int,
         g = _require_native()
         packed = torch.empty((n + 1) // 2, dtype=torch.uint8, device=x.device)
         minmax = torch.empty((nchunks, 2), dtype=torch.float32, device=x.device)
-        res = residual.reshape(-1) if residual is not None else torch.Tensor()
+        res = _flat_inplace(residual, "residual") \
+            if residual is not None else torch.Tensor()
         g.quantize_4bit(x.reshape(-1), res, packed, minmax, chunk_elems)
         return packed, minmax
     packs, mins, maxs = [], [], []
@@ -235,7 +250,8 @@ def dequantize_4bit_chunked(packed: torch.Tensor, minmax: torch.Tensor,
         g = _require_native()
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=packed.device)
-        g.dequantize_4bit(packed, minmax, out.reshape(-1), chunk_elems)
+        g.dequantize_4bit(packed, minmax, _flat_inplace(out, "out"),
+                          chunk_elems)
         return out
     res = []
     # CPU reference packs each chunk independently (chunk_elems even except last)
@@ -258,15 +274,17 @@ def dequantize_4bit_chunked(packed: torch.Tensor, minmax: torch.Tensor,
 
 def sgd_update(w, g, lr, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().sgd_update(w.reshape(-1), g.reshape(-1), lr, wd, rescale)
+        _require_native().sgd_update(_flat_inplace(w, "w"), g.reshape(-1),
+                                     lr, wd, rescale)
         return
     ref.sgd_update(w, g, lr, wd, rescale)
 
 
 def sgd_mom_update(w, g, mom, lr, momentum=0.9, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().sgd_mom_update(w.reshape(-1), g.reshape(-1),
-                                         mom.reshape(-1), lr, momentum, wd, rescale)
+        _require_native().sgd_mom_update(
+            _flat_inplace(w, "w"), g.reshape(-1), _flat_inplace(mom, "mom"),
+            lr, momentum, wd, rescale)
         return
     ref.sgd_mom_update(w, g, mom, lr, momentum, wd, rescale)
 
@@ -274,43 +292,44 @@ def sgd_mom_update(w, g, mom, lr, momentum=0.9, wd=0.0, rescale=1.0):
 def adam_update(w, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0,
                 rescale=1.0):
     if _on_gpu(w):
-        _require_native().adam_update(w.reshape(-1), g.reshape(-1),
-                                      m.reshape(-1), v.reshape(-1),
-                                      t, lr, beta1, beta2, eps, wd, rescale)
+        _require_native().adam_update(
+            _flat_inplace(w, "w"), g.reshape(-1), _flat_inplace(m, "m"),
+            _flat_inplace(v, "v"), t, lr, beta1, beta2, eps, wd, rescale)
         return
     ref.adam_update(w, g, m, v, t, lr, beta1, beta2, eps, wd, rescale)
 
 
 def rmsprop_update(w, g, n, lr, rho=0.9, eps=1e-8, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().rmsprop_update(w.reshape(-1), g.reshape(-1),
-                                         n.reshape(-1), lr, rho, eps, wd,
-                                         rescale)
+        _require_native().rmsprop_update(
+            _flat_inplace(w, "w"), g.reshape(-1), _flat_inplace(n, "n"),
+            lr, rho, eps, wd, rescale)
         return
     ref.rmsprop_update(w, g, n, lr, rho, eps, wd, rescale)
 
 
 def adagrad_update(w, g, h, lr, eps=1e-7, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().adagrad_update(w.reshape(-1), g.reshape(-1),
-                                         h.reshape(-1), lr, eps, wd, rescale)
+        _require_native().adagrad_update(
+            _flat_inplace(w, "w"), g.reshape(-1), _flat_inplace(h, "h"),
+            lr, eps, wd, rescale)
         return
     ref.adagrad_update(w, g, h, lr, eps, wd, rescale)
 
 
 def signsgd_update(w, g, lr, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().signsgd_update(w.reshape(-1), g.reshape(-1), lr,
-                                         wd, rescale)
+        _require_native().signsgd_update(_flat_inplace(w, "w"),
+                                         g.reshape(-1), lr, wd, rescale)
         return
     ref.signsgd_update(w, g, lr, wd, rescale)
 
 
 def signum_update(w, g, mom, lr, momentum=0.9, wd=0.0, rescale=1.0):
     if _on_gpu(w):
-        _require_native().signum_update(w.reshape(-1), g.reshape(-1),
-                                        mom.reshape(-1), lr, momentum, wd,
-                                        rescale)
+        _require_native().signum_update(
+            _flat_inplace(w, "w"), g.reshape(-1), _flat_inplace(mom, "mom"),
+            lr, momentum, wd, rescale)
         return
     ref.signum_update(w, g, mom, lr, momentum, wd, rescale)
 
@@ -318,9 +337,13 @@ def signum_update(w, g, mom, lr, momentum=0.9, wd=0.0, rescale=1.0):
 def dcasgd_update(w, g, prev_w, mom, lr, lamda=0.04, momentum=0.0, wd=0.0,
                   rescale=1.0):
     if _on_gpu(w):
+        # as the golden model: a momentum state is used (and written) only
+        # when momentum != 0; otherwise the kernel gets no state at all
+        use_mom = mom is not None and momentum != 0.0
         _require_native().dcasgd_update(
-            w.reshape(-1), g.reshape(-1), prev_w.reshape(-1),
-            mom.reshape(-1) if mom is not None else torch.Tensor(),
+            _flat_inplace(w, "w"), g.reshape(-1),
+            _flat_inplace(prev_w, "prev_w"),
+            _flat_inplace(mom, "mom") if use_mom else torch.Tensor(),
             lr, lamda, momentum, wd, rescale)
         return
     ref.dcasgd_update(w, g, prev_w, mom, lr, lamda, momentum, wd, rescale)

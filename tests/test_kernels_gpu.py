@@ -38,7 +38,8 @@ def test_quantize_2bit_matches_reference(n):
     packed_gpu = ops.quantize_2bit(g, r_gpu, thr)
     packed_cpu = ref.quantize_2bit(g.cpu(), r_cpu, thr)
     assert torch.equal(packed_gpu.cpu(), packed_cpu)
-    assert torch.allclose(r_gpu.cpu(), r_cpu, atol=1e-6)
+    # one fp32 add and one subtract per element: bit-equal
+    assert torch.equal(r_gpu.cpu(), r_cpu)
     # dequantize round-trip
     deq_gpu = ops.dequantize_2bit(packed_gpu, n, thr)
     deq_cpu = ref.dequantize_2bit(packed_cpu, n, thr)
@@ -53,7 +54,11 @@ def test_quantize_2bit_residual_chain():
         packed = ops.quantize_2bit(g, r, 1.0)
         d = ops.dequantize_2bit(packed, n, 1.0)
         assert torch.all(d == expect), expect
-    assert torch.allclose(r, torch.full((n,), 0.2, device=DEV), atol=1e-5)
+    # the same three fp32 adds and one subtract on the host
+    expect = torch.full((n,), 0.4)
+    expect = expect + 0.4
+    expect = expect + 0.4 - 1.0
+    assert torch.equal(r.cpu(), expect)
 
 
 # ---------------------------------------------------------------------------
@@ -81,9 +86,9 @@ def test_bsc_pack_matches_reference_fixed_boundary(n):
     v_c = torch.zeros(n)
     vals_c, idx_c = ref.bsc_compress(g, u_c, v_c, ratio, boundary=boundary)
     assert torch.equal(idx_g.cpu(), idx_c)
-    assert torch.allclose(vals_g.cpu(), vals_c, atol=1e-6)
-    assert torch.allclose(u_g.cpu(), u_c, atol=1e-6)
-    assert torch.allclose(v_g.cpu(), v_c, atol=1e-6)
+    assert torch.equal(vals_g.cpu(), vals_c)
+    assert torch.equal(u_g.cpu(), u_c)
+    assert torch.equal(v_g.cpu(), v_c)
 
 
 def test_bsc_full_pipeline_roundtrip():
@@ -100,10 +105,11 @@ def test_bsc_full_pipeline_roundtrip():
     assert sent.sum() > 0
     out = ops.bsc_decompress(vals, idx, n)
     ii = idx[sent].long()
-    assert torch.allclose(out[ii], g[ii], atol=1e-5)
+    assert torch.equal(out[ii], g[ii])
     assert torch.all(v[ii] == 0)
-    # conservation: out + v == g everywhere (momentum first step: v=g)
-    assert torch.allclose(out + v, g, atol=1e-5)
+    # conservation: out + v == g everywhere (momentum first step: v=g,
+    # and one of out, v is 0 at every position: exact)
+    assert torch.equal(out + v, g)
 
 
 def test_bsc_pull_pack_matches_reference():
@@ -116,7 +122,7 @@ def test_bsc_pull_pack_matches_reference():
     vals_g, idx_g = ops.bsc_pull_compress(x.to(DEV), cap)
     vals_c, idx_c = ref.bsc_pull_compress(x, cap)
     assert torch.equal(idx_g.cpu(), idx_c)
-    assert torch.allclose(vals_g.cpu(), vals_c, atol=1e-6)
+    assert torch.equal(vals_g.cpu(), vals_c)
 
 
 def test_bsc_unpack_accumulate():
@@ -274,7 +280,7 @@ def test_bsc_pack_ragged_sizes():
         mask = v_c.abs() >= boundary
         sel = mask.nonzero().flatten()[:k]
         assert torch.equal(idx_g.cpu()[:sel.numel()].long(), sel)
-        assert torch.allclose(vals_g.cpu()[:sel.numel()], g[sel], atol=1e-6)
+        assert torch.equal(vals_g.cpu()[:sel.numel()], g[sel])
         assert (idx_g.cpu()[sel.numel():] == -1).all()
 
 
@@ -291,7 +297,8 @@ def test_fused_relu_pool_matches_aten():
     g = torch.randn_like(y)
     y.backward(g)
     ref_y.backward(g)
-    # backward can differ on exact ties; random bf16 ties are measure-zero
+    # ties (common in bf16) go to the first maximum, as in ATen; they are
+    # tested on purpose in test_kvstore_kernels_edges_gpu.py
     assert torch.equal(x.grad, ref_x.grad)
 
 
@@ -601,15 +608,12 @@ def test_bsc_fused_matches_cpu_reference(n):
         g = torch.randn(n) * (step + 1)
         vals_g, idx_g = ops.bsc_compress(g.to(DEV), u_g, v_g, ratio)
         vals_c, idx_c = ref.bsc_compress(g, u_c, v_c, ratio)
-        sel_g = int((idx_g >= 0).sum())
-        sel_c = int((idx_c >= 0).sum())
-        # boundary ties can differ by a few ulp-equal elements at most
-        assert abs(sel_g - sel_c) <= max(2, sel_c // 1000), (sel_g, sel_c)
-        k = min(sel_g, sel_c)
-        assert torch.equal(idx_g[:k].cpu(), idx_c[:k]), step
-        assert torch.allclose(vals_g[:k].cpu(), vals_c[:k], atol=1e-5)
-        assert torch.allclose(u_g.cpu(), u_c, atol=1e-5)
-        assert torch.allclose(v_g.cpu(), v_c, atol=1e-5)
+        # the kernel rounds u*mu and + g separately, as the model and the
+        # boundary prediction do: the same elements, bit for bit
+        assert torch.equal(idx_g.cpu(), idx_c), step
+        assert torch.equal(vals_g.cpu(), vals_c), step
+        assert torch.equal(u_g.cpu(), u_c), step
+        assert torch.equal(v_g.cpu(), v_c), step
 
 
 def test_bsc_fused_capacity_bound():
