@@ -12,6 +12,10 @@
 //                          (the data-gradient GEMM's weight operand)
 //   k_fc_w_unpermute_f32   bf16 [O][HW][C] -> fp32 [O][C][HW]
 //                          (replaces the weight gradient's bf16 -> fp32)
+//   k_fc_w_pack2_bf16      the permute kernel plus the forward GEMM's
+//                          plain bf16 cast, from one read of the weight
+//   k_fc_w_unpermute_into  the un-permute, written into a caller-given
+//                          span (the trainer's gradient bucket)
 //
 // The forward GEMM reduces over K, so it keeps the (c, h, w) order and
 // its rounding; its activation copy is k_fc_flatten_nchw, an LDS-tiled
@@ -83,8 +87,84 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_w_permute_bf16(
   }
 }
 
-// bf16 [O][HW][32] -> fp32 [O][32][HW]: the mirror image.
-__global__ __launch_bounds__(FC_THREADS) void k_fc_w_unpermute_f32(
+// Both bf16 layouts of the weight from ONE read of the fp32 master:
+//   wb  bf16 [O][32][HW]  the forward GEMM's operand (weight order)
+//   wp  bf16 [O][HW][32]  the data-gradient operand, as the permute
+//                         kernel writes it; wp == nullptr skips it
+// Same block as k_fc_w_permute_bf16 (one per (o, 128-pixel tile), the
+// [32][129] fp32 tile, fc_f2bf); the wp half is that kernel's code. The
+// wb half walks along hw the way k_fc_flatten_nchw does: HW may be odd,
+// so a channel row is only 2 B aligned; pairs are taken on even GLOBAL
+// element indices (4 B stores), and the one or two elements a tile has
+// left over at its ends go out as 2 B stores. wb itself is 4 B aligned.
+__global__ __launch_bounds__(FC_THREADS) void k_fc_w_pack2_bf16(
+    const float* __restrict__ w, bf16_t* __restrict__ wb,
+    bf16_t* __restrict__ wp, int HW) {
+  __shared__ float tile[FC_C * FC_PERM_LD];
+  const int t = threadIdx.x;
+  const int hw0 = blockIdx.x * FC_PERM_HW;  // even
+  const long long o = blockIdx.y;
+  const float* src = w + o * FC_C * HW;
+  {
+    const int hw = t & (FC_PERM_HW - 1), c0 = t >> 7;
+    if (hw0 + hw < HW) {
+      float v[FC_C / 2];
+#pragma unroll
+      for (int i = 0; i < FC_C / 2; ++i)
+        v[i] = src[(long long)(c0 + 2 * i) * HW + hw0 + hw];
+#pragma unroll
+      for (int i = 0; i < FC_C / 2; ++i)
+        tile[(c0 + 2 * i) * FC_PERM_LD + hw] = v[i];
+    }
+  }
+  __syncthreads();
+  if (wp != nullptr) {
+    bf16_t* dst = wp + o * HW * FC_C;
+    const int cg = t & 3;  // channel group of 8
+#pragma unroll
+    for (int p = 0; p < FC_PERM_HW / (FC_THREADS / 4); ++p) {
+      const int hw = p * (FC_THREADS / 4) + (t >> 2);
+      if (hw0 + hw < HW) {
+        union { bf16x8 v; bf16_t e[8]; } pk;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          pk.e[j] = fc_f2bf(tile[(cg * 8 + j) * FC_PERM_LD + hw]);
+        *reinterpret_cast<bf16x8*>(dst + (long long)(hw0 + hw) * FC_C +
+                                   cg * 8) = pk.v;
+      }
+    }
+  }
+  const int wave = t >> 6, lane = t & 63;
+#pragma unroll
+  for (int i = 0; i < FC_C / 4; ++i) {
+    const int c = wave * (FC_C / 4) + i;
+    const long long row = (o * FC_C + c) * HW + hw0;  // first element
+    const int par = (int)(row & 1);
+    const float* trow = tile + c * FC_PERM_LD;
+    bf16_t* dst = wb + row;
+    const int e0 = 2 * lane - par, e1 = e0 + 1;  // row + e0 is even
+    const bool ok0 = e0 >= 0 && hw0 + e0 < HW;
+    const bool ok1 = hw0 + e1 < HW;
+    if (ok0 && ok1) {
+      const unsigned v = (unsigned)fc_f2bf(trow[e0]) |
+                         ((unsigned)fc_f2bf(trow[e1]) << 16);
+      *reinterpret_cast<unsigned*>(dst + e0) = v;
+    } else if (ok0) {
+      dst[e0] = fc_f2bf(trow[e0]);
+    } else if (ok1) {
+      dst[e1] = fc_f2bf(trow[e1]);
+    }
+    // an odd row leaves the tile's last element unpaired
+    if (par && lane == 0 && hw0 + FC_PERM_HW - 1 < HW)
+      dst[FC_PERM_HW - 1] = fc_f2bf(trow[FC_PERM_HW - 1]);
+  }
+}
+
+// bf16 [O][HW][32] -> fp32 [O][32][HW]: the mirror image. kPosZero
+// stores x + 0.0f, the value `0 + x` of an accumulation into a cleared
+// buffer: a -0 becomes +0, everything else keeps its bits.
+template <bool kPosZero>
+__device__ __forceinline__ void fc_w_unpermute_body(
     const bf16_t* __restrict__ gp, float* __restrict__ g, int HW) {
   __shared__ float tile[FC_C * FC_PERM_LD];
   const int t = threadIdx.x;
@@ -112,10 +192,24 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_w_unpermute_f32(
   const int hw = t & (FC_PERM_HW - 1), c0 = t >> 7;
   if (hw0 + hw < HW) {
 #pragma unroll
-    for (int i = 0; i < FC_C / 2; ++i)
-      dst[(long long)(c0 + 2 * i) * HW + hw0 + hw] =
-          tile[(c0 + 2 * i) * FC_PERM_LD + hw];
+    for (int i = 0; i < FC_C / 2; ++i) {
+      const float v = tile[(c0 + 2 * i) * FC_PERM_LD + hw];
+      dst[(long long)(c0 + 2 * i) * HW + hw0 + hw] = kPosZero ? v + 0.0f : v;
+    }
   }
+}
+
+__global__ __launch_bounds__(FC_THREADS) void k_fc_w_unpermute_f32(
+    const bf16_t* __restrict__ gp, float* __restrict__ g, int HW) {
+  fc_w_unpermute_body<false>(gp, g, HW);
+}
+
+// The same into a caller-given dense [O][32*HW] destination that may
+// start at any 4 B-aligned address inside a larger buffer (the stores
+// are dword-wise): the weight gradient written where it is consumed.
+__global__ __launch_bounds__(FC_THREADS) void k_fc_w_unpermute_into(
+    const bf16_t* __restrict__ gp, float* __restrict__ g, int HW) {
+  fc_w_unpermute_body<true>(gp, g, HW);
 }
 
 // Flatten of a channels_last activation: bf16 [N][HW][32] -> bf16
@@ -197,6 +291,24 @@ int geops_fc_w_unpermute_f32(const bf16_t* gp, float* g, int O, int C, int HW,
                              hipStream_t s) {
   if (!fc_geometry_ok(O, C, HW)) return -1;
   hipLaunchKernelGGL(k_fc_w_unpermute_f32,
+                     dim3((HW + FC_PERM_HW - 1) / FC_PERM_HW, O),
+                     dim3(FC_THREADS), 0, s, gp, g, HW);
+  return 0;
+}
+
+int geops_fc_w_pack2_bf16(const float* w, bf16_t* wb, bf16_t* wp, int O,
+                          int C, int HW, hipStream_t s) {
+  if (!fc_geometry_ok(O, C, HW)) return -1;
+  hipLaunchKernelGGL(k_fc_w_pack2_bf16,
+                     dim3((HW + FC_PERM_HW - 1) / FC_PERM_HW, O),
+                     dim3(FC_THREADS), 0, s, w, wb, wp, HW);
+  return 0;
+}
+
+int geops_fc_w_unpermute_into(const bf16_t* gp, float* g, int O, int C,
+                              int HW, hipStream_t s) {
+  if (!fc_geometry_ok(O, C, HW)) return -1;
+  hipLaunchKernelGGL(k_fc_w_unpermute_into,
                      dim3((HW + FC_PERM_HW - 1) / FC_PERM_HW, O),
                      dim3(FC_THREADS), 0, s, gp, g, HW);
   return 0;

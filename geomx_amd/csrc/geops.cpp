@@ -118,6 +118,10 @@ int geops_fc_w_unpermute_f32(const unsigned short*, float*, int, int, int,
                              hipStream_t);
 int geops_fc_flatten_nchw(const unsigned short*, unsigned short*, int, int,
                           int, hipStream_t);
+int geops_fc_w_pack2_bf16(const float*, unsigned short*, unsigned short*,
+                          int, int, int, hipStream_t);
+int geops_fc_w_unpermute_into(const unsigned short*, float*, int, int, int,
+                              hipStream_t);
 void geops_tr16_probe(const unsigned short*, unsigned short*, hipStream_t);
 void geops_tr16_probe2(const unsigned short*, const int*, unsigned short*,
                        hipStream_t);
@@ -593,6 +597,82 @@ torch::Tensor fc_w_unpermute_f32(torch::Tensor gp, int64_t O, int64_t C,
   return g;
 }
 
+// The kernels are launched on the current stream, which belongs to the
+// current device: an operand from another device would be written by a
+// queue that does not own it.
+void check_on_current_device(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.get_device() == at::cuda::current_device(), name,
+              " is on device ", t.get_device(),
+              ", the current device is ", (int)at::cuda::current_device());
+}
+
+// fp32 master weight [O][C*HW] -> (wb, wp): wb bf16 [O][C*HW], the bits
+// of w.to(bfloat16) (the forward GEMM's operand), and, with want_perm,
+// wp bf16 [O][HW*C], the bits of fc_w_permute_bf16(w); otherwise wp is
+// None and that half is skipped. One read of the weight serves both.
+// wb_out / wp_out place the outputs in caller-given storage (wb needs
+// 4 B alignment, wp 16 B); by default both are freshly allocated.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> fc_w_pack2_bf16(
+    torch::Tensor w, int64_t O, int64_t C, int64_t HW, bool want_perm,
+    c10::optional<torch::Tensor> wb_out,
+    c10::optional<torch::Tensor> wp_out) {
+  check_fc_operand(w, torch::kFloat32, O * C * HW, "weight");
+  check_on_current_device(w, "weight");
+  const auto opts = w.options().dtype(torch::kBFloat16);
+  torch::Tensor wb;
+  if (wb_out.has_value()) {
+    wb = *wb_out;
+    TORCH_CHECK(wb.is_cuda() && wb.is_contiguous() &&
+                    wb.scalar_type() == torch::kBFloat16 &&
+                    wb.numel() == O * C * HW,
+                "wb_out must be a contiguous GPU bf16 tensor of ",
+                O * C * HW, " elements");
+    TORCH_CHECK(((uintptr_t)wb.data_ptr() & 3) == 0,
+                "wb_out must be 4-byte aligned");
+    TORCH_CHECK(wb.device() == w.device(),
+                "wb_out must be on the weight's device");
+  } else {
+    wb = torch::empty({O, C * HW}, opts);
+  }
+  c10::optional<torch::Tensor> wp;
+  if (want_perm) {
+    if (wp_out.has_value()) {
+      check_fc_operand(*wp_out, torch::kBFloat16, O * C * HW, "wp_out");
+      TORCH_CHECK(wp_out->device() == w.device(),
+                  "wp_out must be on the weight's device");
+      wp = *wp_out;
+    } else {
+      wp = torch::empty({O, HW * C}, opts);
+    }
+  }
+  const int rc = geops_fc_w_pack2_bf16(
+      w.data_ptr<float>(), (unsigned short*)wb.data_ptr(),
+      wp.has_value() ? (unsigned short*)wp->data_ptr() : nullptr, (int)O,
+      (int)C, (int)HW, cur_stream());
+  TORCH_CHECK(rc == 0, "fc_w_pack2_bf16: unsupported geometry O=", O,
+              " C=", C, " HW=", HW);
+  launch_check("fc_w_pack2_bf16");
+  return {wb, wp};
+}
+
+// fc_w_unpermute_f32 into a caller-given dense fp32 destination of
+// O*C*HW elements (any 4 B-aligned offset of a larger buffer), with a
+// -0 stored as +0: the bytes `zeros + fc_w_unpermute_f32(gp)` has.
+void fc_w_unpermute_into(torch::Tensor gp, torch::Tensor dst, int64_t O,
+                         int64_t C, int64_t HW) {
+  check_fc_operand(gp, torch::kBFloat16, O * C * HW, "permuted gradient");
+  check_fc_operand(dst, torch::kFloat32, O * C * HW, "destination");
+  TORCH_CHECK(dst.device() == gp.device(),
+              "destination must be on the permuted gradient's device");
+  check_on_current_device(gp, "permuted gradient");
+  const int rc = geops_fc_w_unpermute_into(
+      (const unsigned short*)gp.data_ptr(), dst.data_ptr<float>(), (int)O,
+      (int)C, (int)HW, cur_stream());
+  TORCH_CHECK(rc == 0, "fc_w_unpermute_into: unsupported geometry O=", O,
+              " C=", C, " HW=", HW);
+  launch_check("fc_w_unpermute_into");
+}
+
 // channels_last activation [N][HW*C] -> NCHW-flatten order [N][C*HW],
 // bit-exact with torch.flatten(x, 1) of the channels_last tensor.
 torch::Tensor fc_flatten_nchw(torch::Tensor x, int64_t N, int64_t C,
@@ -885,6 +965,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
   m.def("fc_flatten_nchw", &fc_flatten_nchw);
+  m.def("fc_w_pack2_bf16", &fc_w_pack2_bf16, py::arg("w"), py::arg("O"),
+        py::arg("C"), py::arg("HW"), py::arg("want_perm"),
+        py::arg("wb_out") = py::none(), py::arg("wp_out") = py::none());
+  m.def("fc_w_unpermute_into", &fc_w_unpermute_into);
   m.def("tr16_probe2", [](torch::Tensor in, torch::Tensor addr,
                           torch::Tensor out) {
     TORCH_CHECK(in.is_cuda() && addr.is_cuda() && out.is_cuda());

@@ -14,12 +14,20 @@ columns and every output element is the same sum in the same order.
     rounding, and a training run amplifies that, so it keeps the NCHW
     order); only the flatten copy itself is a tiled transpose kernel
     (k_fc_flatten_nchw) instead of a strided elementwise copy;
-  * data gradient: dy @ Wp with Wp the weight cast AND permuted to bf16
-    [O][HW][C] (k_fc_w_permute_bf16); the result is already the NHWC
-    gradient the conv backward wants, returned as a channels_last view;
+  * both bf16 copies of the weight come from one read of the fp32
+    master in forward (k_fc_w_pack2_bf16): the plain cast the GEMM
+    takes, and, when the input needs a gradient, the cast-AND-permuted
+    [O][HW][C] operand of the data-gradient GEMM, which rides on the
+    autograd context to backward;
+  * data gradient: dy @ Wp; the result is already the NHWC gradient the
+    conv backward wants, returned as a channels_last view;
   * weight gradient: dy^T @ x on the channels_last activation as it
-    is, then cast AND un-permuted to fp32 [O][C][HW]
-    (k_fc_w_unpermute_f32), in place of the plain bf16 -> fp32 cast.
+    is, then cast AND un-permuted to fp32 [O][C][HW], in place of the
+    plain bf16 -> fp32 cast. Under a trainer that attached a gradient
+    sink to the weight (geomx_amd/gradsink.py) the un-permute writes
+    straight into the weight's span of the gradient bucket
+    (k_fc_w_unpermute_into) and that view is the returned gradient;
+    otherwise it is a fresh tensor (k_fc_w_unpermute_f32).
 
 The module's parameters are exactly nn.Linear's (weight [O, C*H*W] in
 NCHW-flatten order), so state dicts and checkpoints are interchangeable
@@ -33,6 +41,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
+from .. import gradsink
 from . import native_available
 
 FC_CHANNELS = 32   # k_fc_w_*: a pixel's channels are one 64 B record
@@ -76,14 +85,19 @@ class _FlattenLinearFn(torch.autograd.Function):
         N, C, H, W = x.shape
         xf = x.detach().to(torch.bfloat16).permute(0, 2, 3, 1) \
             .reshape(N, H * W * C)         # a view: x is NHWC-dense
+        # weight.to(bfloat16) and, if backward will want it, the
+        # permuted data-gradient operand: one read of the fp32 weight
+        wb, wp = _geops.fc_w_pack2_bf16(weight.detach(), weight.shape[0],
+                                        C, H * W, ctx.needs_input_grad[0])
         # torch.flatten(x, 1) as a tiled transpose, the casts autocast
         # would make, then the same library GEMM on the same operands
         with torch.autocast("cuda", enabled=False):
-            y = F.linear(_geops.fc_flatten_nchw(xf, N, C, H * W),
-                         weight.detach().to(torch.bfloat16),
+            y = F.linear(_geops.fc_flatten_nchw(xf, N, C, H * W), wb,
                          None if bias is None
                          else bias.detach().to(torch.bfloat16))
-        ctx.save_for_backward(xf, weight)
+        ctx.save_for_backward(xf)
+        ctx.wp = wp
+        ctx.sink = gradsink.sink_of(weight)
         ctx.geom = (N, C, H, W, weight.shape[0])
         ctx.x_dtype = x.dtype
         ctx.b_dtype = None if bias is None else bias.dtype
@@ -92,19 +106,24 @@ class _FlattenLinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         from geomx_amd import _geops
-        xf, weight = ctx.saved_tensors
+        xf, = ctx.saved_tensors
         N, C, H, W, O = ctx.geom
         dy = grad_out.to(torch.bfloat16).contiguous()
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
             # [N][HW*C] IS the NHWC gradient: hand it on as a
             # channels_last view, no copy
-            wp = _geops.fc_w_permute_bf16(weight.detach(), O, C, H * W)
-            grad_x = torch.mm(dy, wp).view(N, H, W, C).permute(0, 3, 1, 2) \
+            grad_x = torch.mm(dy, ctx.wp).view(N, H, W, C).permute(0, 3, 1, 2) \
                 .to(ctx.x_dtype)
         if ctx.needs_input_grad[1]:
-            grad_w = _geops.fc_w_unpermute_f32(torch.mm(dy.t(), xf), O, C,
-                                               H * W)
+            gp = torch.mm(dy.t(), xf)
+            # the weight's span of the trainer's gradient bucket, once
+            # per zero_grad(); returned so that autograd adopts it
+            grad_w = None if ctx.sink is None else ctx.sink.take()
+            if grad_w is not None:
+                _geops.fc_w_unpermute_into(gp, grad_w, O, C, H * W)
+            else:
+                grad_w = _geops.fc_w_unpermute_f32(gp, O, C, H * W)
         if ctx.b_dtype is not None and ctx.needs_input_grad[2]:
             grad_b = dy.sum(0).to(ctx.b_dtype)
         return grad_x, grad_w, grad_b
@@ -113,6 +132,11 @@ class _FlattenLinearFn(torch.autograd.Function):
 class GeoFlattenLinear(torch.nn.Linear):
     """Drop-in for nn.Flatten() -> nn.Linear(C*H*W, O) that takes the
     4-D feature map."""
+
+    def grad_sink_parameters(self):
+        """The parameters whose gradient the backward can write in place
+        (gradsink.py): the weight."""
+        return (self.weight,)
 
     def forward(self, x):
         if native_route(x, self.weight):

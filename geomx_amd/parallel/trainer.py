@@ -13,7 +13,10 @@ This is the performance engine behind both benchmark modes:
 Design notes (MI355X-first):
   * Gradients are made VIEWS into flat fp32 buckets at registration, so
     backward writes grads directly into communication buffers — no
-    pack pass on the critical path.
+    pack pass on the critical path. A parameter whose op can write
+    its gradient anywhere gets a gradient sink (gradsink.py): its span
+    is neither cleared by zero_grad() nor added into, the op's backward
+    writes the gradient there and autograd adopts the view.
   * Buckets are formed in REVERSE parameter order: autograd produces
     grads from the last layer backwards, so a bucket completes as early
     as possible and its collective overlaps the rest of backward. This
@@ -39,7 +42,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from .. import comm, ops
+from .. import comm, gradsink, ops
 from ..config import Config
 from ..kvstore.optimizer import OptimizerSpec, ServerOptimizer
 from ..kvstore.wan import TokenBucket, cross_party_bytes
@@ -49,7 +52,7 @@ from ..topology import Topology
 class _Bucket:
     __slots__ = ("params", "flat", "param_flat", "views", "ready", "expected",
                  "work", "index", "bsc_u", "bsc_v", "dgt", "res2bit",
-                 "wan_buf", "wan_work", "wan_ready")
+                 "wan_buf", "wan_work", "wan_ready", "clear")
 
     def __init__(self, index: int):
         self.index = index
@@ -57,6 +60,9 @@ class _Bucket:
         self.flat: Optional[torch.Tensor] = None        # gradient bucket
         self.param_flat: Optional[torch.Tensor] = None  # fp32 parameter bucket
         self.views: List[torch.Tensor] = []
+        # what zero_grad() fills: the maximal contiguous ranges of
+        # `flat` outside every gradient-sink span
+        self.clear: List[torch.Tensor] = []
         self.ready = 0
         self.expected = 0
         self.work = None
@@ -100,10 +106,15 @@ def _alias_view(flat: torch.Tensor, off: int, p: torch.Tensor) -> torch.Tensor:
 class GeoTrainer:
     def __init__(self, model: torch.nn.Module, cfg: Config, topo: Topology,
                  optimizer: Optional[OptimizerSpec] = None,
-                 mode: str = "flat"):
+                 mode: str = "flat", grad_sinks: bool = True):
+        """`grad_sinks=False` attaches no gradient sink (gradsink.py):
+        every span is cleared by zero_grad() and filled by autograd's
+        accumulation, whatever the modules offer."""
         if mode not in ("flat", "hips"):
             raise ValueError(mode)
         self.model = model
+        self._use_sinks = grad_sinks
+        self._settled = False   # _settle_grads ran since the last change
         self.cfg = cfg
         self.topo = topo
         self.mode = mode if topo.world_size > 1 else "flat"
@@ -166,6 +177,15 @@ class GeoTrainer:
         def aligned(n):
             return (n + ALIGN - 1) // ALIGN * ALIGN
 
+        # parameters whose module can write the gradient in place
+        sinkable = set()
+        if self._use_sinks:
+            for m in self.model.modules():
+                offer = getattr(m, "grad_sink_parameters", None)
+                if offer is not None:
+                    sinkable.update(id(p) for p in offer())
+        self.sinks: Dict[torch.nn.Parameter, gradsink.GradSink] = {}
+
         for b in self.buckets:
             total = sum(aligned(p.numel()) for p in b.params)
             b.flat = torch.zeros(total, dtype=torch.float32, device=self.device)
@@ -176,6 +196,7 @@ class GeoTrainer:
             b.param_flat = torch.zeros(total, dtype=torch.float32,
                                        device=self.device)
             off = 0
+            lo = 0   # start of the current run of non-sink elements
             for p in b.params:
                 n = p.numel()
                 view = _alias_view(b.flat, off, p)
@@ -187,7 +208,17 @@ class GeoTrainer:
                     pview.copy_(p.data.float())
                 p.data = pview
                 self.param_bucket[p] = (b, len(b.views) - 1)
+                gradsink.detach(p)   # a sink of an earlier trainer
+                if id(p) in sinkable:
+                    sink = gradsink.GradSink(b.flat, view, p)
+                    gradsink.attach(p, sink)
+                    self.sinks[p] = sink
+                    if off > lo:
+                        b.clear.append(b.flat[lo:off])
+                    lo = off + n   # the span's own padding is cleared
                 off += aligned(n)
+            if total > lo:
+                b.clear.append(b.flat[lo:total])
 
     def _register_hooks(self):
         self._hook_handles = []
@@ -196,7 +227,27 @@ class GeoTrainer:
             self._hook_handles.append(h)
 
     def _on_grad_ready(self, p: torch.nn.Parameter):
-        b, _ = self.param_bucket[p]
+        b, i = self.param_bucket[p]
+        # the gradient has to BE the bucket span. It is when autograd
+        # added into the attached view, or adopted the view a sink
+        # handed to the op's backward. It is not when p.grad was None
+        # and autograd installed a tensor of its own (the op took no
+        # sink, autograd cloned or summed several contributions, or a
+        # plain model.zero_grad() dropped the view): copy it in.
+        view = b.views[i]
+        g = p.grad
+        if g is not None and (g.data_ptr() != view.data_ptr()
+                              or g.dtype != view.dtype
+                              or g.stride() != view.stride()):
+            with torch.no_grad():
+                view.copy_(g)
+            p.grad = view
+        # p.grad aliases the span from here on: a sink that this
+        # backward did not use must not hand the span out any more
+        sink = self.sinks.get(p)
+        if sink is not None:
+            sink.disarm()
+        self._settled = False
         b.ready += 1
         if b.ready == b.expected:
             self._launch_bucket(b)
@@ -247,7 +298,26 @@ class GeoTrainer:
         self.allreduce_grads()
         self.update(batch_size=batch_size, lr=lr)
 
+    def _settle_grads(self):
+        """A parameter that received no gradient since its p.grad was
+        dropped (a sink parameter after zero_grad(), any parameter after
+        a plain model.zero_grad()) contributes zero: clear its span and
+        re-attach the view, so that everything that reads the bucket
+        sees what p.grad says. Its sink, if any, is spent: p.grad
+        aliases the span again. Runs once per step, where the buckets
+        are first read."""
+        if self._settled:
+            return
+        for p, (b, i) in self.param_bucket.items():
+            if p.grad is None:
+                b.views[i].zero_()
+                p.grad = b.views[i]
+        for sink in self.sinks.values():
+            sink.disarm()
+        self._settled = True
+
     def _wait_buckets(self):
+        self._settle_grads()
         for b in self.buckets:
             if b.work is not None:
                 b.work.wait()
@@ -278,10 +348,12 @@ class GeoTrainer:
             self.spec.lr = lr
         rs = None if batch_size is None \
             else self.spec.rescale_grad / batch_size
+        self._settle_grads()
         for b in self.buckets:
             self.server_opt.update(("bucket", b.index), b.param_flat,
                                    b.flat, rescale=rs)
             b.ready = 0
+        self._settled = False   # the step is over
 
     # -- pipelined WAN tier (dist_async / MixedSync realized) -----------
     def _wan_tier_async(self):
@@ -334,6 +406,7 @@ class GeoTrainer:
                                             device=b.flat.device)
                 b.wan_ready = 1e-9  # marks a pending apply next step
             b.ready = 0
+        self._settled = False   # the step is over
 
     # -- WAN tier --------------------------------------------------------
     def _wan_tier(self):
@@ -497,9 +570,19 @@ class GeoTrainer:
         self.server_opt.set_learning_rate(lr)
 
     def zero_grad(self):
+        """Clear the gradient buckets. A parameter with a gradient sink
+        is not cleared: its p.grad becomes None and its sink is re-armed,
+        so the next backward writes the gradient into the span (or, off
+        that route, the hook copies it there); until then p.grad is
+        None."""
         for b in self.buckets:
-            b.flat.zero_()
+            for r in b.clear:
+                r.zero_()
             b.ready = 0
+        for p, sink in self.sinks.items():
+            p.grad = None
+            sink.arm()
+        self._settled = False
 
     def refresh_params(self):
         """Re-attach parameters to the flat buffers after an external
