@@ -32,22 +32,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-
-#include "unpool.h"
-
-typedef unsigned short bf16_t;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "conv5_common.h"
 
 #define CONV_THREADS 256  // 4 waves
-
-__device__ __forceinline__ bf16_t cf2bf(float f) {
-  union { float f; unsigned int u; } cv;
-  cv.f = f;
-  unsigned int lsb = (cv.u >> 16) & 1;  // round-to-nearest-even
-  return (bf16_t)((cv.u + 0x7FFFu + lsb) >> 16);
-}
 
 template <int CI, int COT>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
@@ -108,36 +95,12 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
     const long long in_n = (long long)n * Hi * Wi * CI;
     const long long out_row = ((long long)n * Ho + ho) * (long long)Wo * CO;
 
-    // chunked fragment loader (interior-only kernel: loads are always
-    // in-bounds once the lane's pixel is clamped to Wo-1, because
-    // (Wo-1) + 5 taps == Wi exactly). CH frags per chunk keeps the
-    // double-buffer register cost at 2*CH*4 VGPRs regardless of nK.
+    // chunked fragment loader (direct_a_chunk). CH frags per chunk keeps
+    // the double-buffer register cost at 2*CH*4 VGPRs regardless of nK.
     constexpr int CH = (nK >= 8) ? 4 : nK;
     constexpr int nCH = (nK + CH - 1) / CH;
     auto load_chunk = [&](int tw, int c, bf16x8(&dst)[CH]) {
-      const int wo_raw = (tw << 4) + p;
-      const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      const long long e_base = in_n + (long long)wo * CI +
-                               (long long)ho * (Wi * CI);
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        const int km = c * CH + j;
-        const int k0 = km * 32 + q * 8;
-        const int kh = k0 / Sp;
-        const int j0 = k0 % Sp;
-        dst[j] = (bf16x8)0;
-        if (km < nK && k0 < K && j0 < S) {
-          const long long e = e_base + (long long)kh * (Wi * CI) + j0;
-          if (S - j0 >= 8) {
-            dst[j] = *reinterpret_cast<const bf16x8*>(in + e);
-          } else {  // 4 real + 4 zero-pad (conv1's Sp > S)
-            const uint2 v = *reinterpret_cast<const uint2*>(in + e);
-            union { uint4 u; bf16x8 h; } cv;
-            cv.u = make_uint4(v.x, v.y, 0u, 0u);
-            dst[j] = cv.h;
-          }
-        }
-      }
+      direct_a_chunk<CI, CH>(in, in_n, tw, c, p, q, ho, Wi, Wo, dst);
     };
 
     // software pipeline: the NEXT chunk's loads are issued before this
@@ -262,28 +225,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool_nhwc(
         ((long long)n * Hop + hp) * (long long)Wop * CO;
 
     auto load_row = [&](int tw, int r, bf16x8(&dst)[nK]) {
-      const int wo_raw = (tw << 4) + p;
-      const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-      const long long e_base =
-          in_n + (long long)wo * CI + (long long)(ho0 + r) * (Wi * CI);
-#pragma unroll
-      for (int km = 0; km < nK; ++km) {
-        const int k0 = km * 32 + q * 8;
-        const int kh = k0 / Sp;
-        const int j0 = k0 % Sp;
-        dst[km] = (bf16x8)0;
-        if (k0 < K && j0 < S) {
-          const long long e = e_base + (long long)kh * (Wi * CI) + j0;
-          if (S - j0 >= 8) {
-            dst[km] = *reinterpret_cast<const bf16x8*>(in + e);
-          } else {
-            const uint2 v = *reinterpret_cast<const uint2*>(in + e);
-            union { uint4 u; bf16x8 h; } cv;
-            cv.u = make_uint4(v.x, v.y, 0u, 0u);
-            dst[km] = cv.h;
-          }
-        }
-      }
+      direct_a_chunk<CI, nK>(in, in_n, tw, 0, p, q, ho0 + r, Wi, Wo, dst);
     };
 
     bf16x8 af0[nK], af1[nK];
@@ -314,6 +256,8 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool_nhwc(
         const int i0 = pi * 2;
         const int wp = (wo0 + q * 4 + i0) >> 1;
         if (wp >= Wop) continue;
+        // (pool_relu4 written out: through the helper this kernel
+        // measured 0.35 % slower, docs/kernels.md)
         const float q0 = a0[i0] + bias_v;      // (dy,dx)=(0,0)
         const float q1 = a0[i0 + 1] + bias_v;  // (0,1)
         const float q2 = a1[i0] + bias_v;      // (1,0)
@@ -368,73 +312,6 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool_nhwc(
 // kernels these replace (and of k_conv5_pool_nhwc), so out and mask are
 // bit-identical to theirs.
 // ---------------------------------------------------------------------
-__device__ __attribute__((aligned(64))) bf16_t g_convp_zeros[1024];
-
-// One 1 KiB LDS-DMA piece (16 B per lane) that the compiler does not
-// see: for a __builtin_amdgcn_global_load_lds in flight hipcc puts
-// s_waitcnt vmcnt(0) ahead of the next LDS read, which would end the
-// prefetch of the next block's image at the first fragment read of this
-// one (same device as convwrw2.hip). The kernels wait for their pieces
-// themselves. `lds_dst` is the wave-uniform LDS byte address.
-__device__ __forceinline__ void glds16_unseen(const void* gsrc,
-                                              unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
-      : "memory");
-}
-
-// bias-added 2x2 window (q0..q3 = (dy,dx) (0,0) (0,1) (1,0) (1,1)) ->
-// pooled bf16 and argmax code; the first maximum wins, <= 0 clamps
-__device__ __forceinline__ void pool_relu4(float q0, float q1, float q2,
-                                           float q3, unsigned& ov,
-                                           unsigned& code) {
-  float mx = q0;
-  unsigned arg = 0;
-  if (q1 > mx) { mx = q1; arg = 1; }
-  if (q2 > mx) { mx = q2; arg = 2; }
-  if (q3 > mx) { mx = q3; arg = 3; }
-  if (mx <= 0.0f) {
-    ov = 0u;
-    code = 255u;
-  } else {
-    ov = cf2bf(mx);
-    code = arg;
-  }
-}
-
-// 4x4 transpose of 16-bit values inside each lane quad (the exchange of
-// the dgrad epilogue): every lane passes v0..v3 for ITS channel m; lane
-// j = m & 3 of the quad returns v_j of channels (m & ~3) .. +3, packed
-// low to high. All 64 lanes must be active.
-__device__ __forceinline__ uint2 quad_tr4(unsigned v0, unsigned v1,
-                                          unsigned v2, unsigned v3, int m) {
-  const unsigned sel1 = (m & 1) ? 0x03020706u : 0x05040100u;
-  const bool lo2 = (m & 3) < 2;
-  const unsigned a = v0 | (v1 << 16);
-  const unsigned b = v2 | (v3 << 16);
-  const unsigned a1 = __builtin_amdgcn_perm(
-      (unsigned)__builtin_amdgcn_mov_dpp((int)a, 0xB1, 0xF, 0xF, true), a,
-      sel1);
-  const unsigned b1 = __builtin_amdgcn_perm(
-      (unsigned)__builtin_amdgcn_mov_dpp((int)b, 0xB1, 0xF, 0xF, true), b,
-      sel1);
-  const unsigned snd = lo2 ? b1 : a1;
-  const unsigned rcv =
-      (unsigned)__builtin_amdgcn_mov_dpp((int)snd, 0x4E, 0xF, 0xF, true);
-  return make_uint2(lo2 ? a1 : rcv, lo2 ? rcv : b1);
-}
-
-// four 16-bit codes (quad_tr4 of codes) -> four bytes
-__device__ __forceinline__ unsigned pack_codes(uint2 c) {
-  return __builtin_amdgcn_perm(c.y, c.x, 0x06040200u);
-}
 
 // conv1 stage. A tile's chunk km reads, per conv row, 16 B at pixel wo
 // of staged row r + kh (two ds_read_b64: odd wo is only 8 B aligned);
@@ -458,14 +335,14 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   constexpr int K = 5 * Sp;             // 120
   constexpr int nK = (K + 31) / 32;     // 4
   constexpr int CO = 16;
-  constexpr int AROW_BYTES = PIX * CI * 2;
-  constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
-  constexpr int ARPB = NCHA * 1024 + 64;  // bank skew per row
+  using Rows = RowImage<PIX, CI, true>;   // bank skew per row
+  constexpr int NCHA = Rows::NCH;
+  constexpr int ARPB = Rows::PITCH;
   constexpr int ROWS = 4;                 // conv rows per block
   constexpr int NROW = ROWS + 4;
   constexpr int IMG = NROW * ARPB;
-  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;  // tiles per wave
-  constexpr int NS = MAXU * nK;                   // steps of the walk
+  constexpr int MAXU = Rows::MAXU;        // tiles per wave
+  constexpr int NS = MAXU * nK;           // steps of the walk
   __shared__ __attribute__((aligned(128))) char lds_rows[2 * IMG];
 
   const int lane = threadIdx.x & 63;
@@ -486,8 +363,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   const long long n_blocks = (long long)Nn * hblocks;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
-  const unsigned lds0 =
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_rows;
+  const unsigned lds0 = lds_addr(lds_rows);
 
   // per-lane read address of (tile u, chunk km) in image 0, conv row 0.
   // A tile past the row clamps to the last pixel: in-bounds, never
@@ -496,7 +372,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   // lie past pixel PIX and are zero-filled in every staged row (a select
   // after the read cost 16 VALU per tile, 0.007 ms at the flagship).
   static_assert((nK - 1) * 32 + 2 * 8 < K && (nK - 1) * 32 + 3 * 8 >= K, "");
-  static_assert(AROW_BYTES + 16 <= NCHA * 1024, "zero tail behind the row");
+  static_assert(Rows::ROW_BYTES + 16 <= NCHA * 1024, "zero tail behind row");
   unsigned aofs[MAXU][nK];
 #pragma unroll
   for (int u = 0; u < MAXU; ++u) {
@@ -516,17 +392,8 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
     const long long n = b / hblocks;
     const int ho0 = (int)(b - n * hblocks) * ROWS;
     const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
-    const int nst = (nrows + 4) * NCHA;
-    for (int t = wid; t < nst; t += 4) {
-      const int ir = t / NCHA;
-      const int c = t - ir * NCHA;
-      const int pix = (c * 64 + lane) * 2;   // 16B = 2 pixels
-      const bf16_t* src =
-          (pix + 1 < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                                 (long long)pix * CI)
-                         : g_convp_zeros;
-      glds16_unseen(src, lds0 + img * IMG + ir * ARPB + c * 1024);
-    }
+    stage_rows<CI, NCHA, ARPB, true>(in, n, Hi, Wi, ho0, (nrows + 4) * NCHA,
+                                     wid, lane, lds0, img * IMG);
   };
 
   // packed results of one block: lane j = m & 3 holds channels
@@ -653,14 +520,14 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_conv5_pool16_nhwc(
   constexpr int K = 5 * S;              // 400
   constexpr int nK = (K + 31) / 32;     // 13
   constexpr int CO = COT * 16;
-  constexpr int AROW_BYTES = PIX * CI * 2;
-  constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
-  constexpr int ARPB = NCHA * 1024 + 64;
+  using Rows = RowImage<PIX, CI, true>;
+  constexpr int NCHA = Rows::NCH;
+  constexpr int ARPB = Rows::PITCH;
   constexpr int ROWS = 4;
   constexpr int NROW = ROWS + 4;
   constexpr int IMG = NROW * ARPB;
   constexpr int NT = nK + 5;            // linear fragments per parity
-  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;
+  constexpr int MAXU = Rows::MAXU;
   constexpr int NS = MAXU * 2 * NT;     // steps of the walk
   static_assert(NT % 3 == 0, "three fragment sets rotate per parity");
   __shared__ __attribute__((aligned(128))) char lds_all[2 * IMG + ARPB];
@@ -686,8 +553,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_conv5_pool16_nhwc(
   const long long n_blocks = (long long)Nn * hblocks;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
-  const unsigned lds0 =
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_all;
+  const unsigned lds0 = lds_addr(lds_all);
 
   // linear fragment t sits at foff[t % 5] + 2 * (t / 5) rows
   unsigned foff[5];
@@ -708,18 +574,8 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void k_conv5_pool16_nhwc(
     const long long n = b / hblocks;
     const int ho0 = (int)(b - n * hblocks) * ROWS;
     const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
-    const int nst = (nrows + 4) * NCHA;
-    for (int t = wid; t < nst; t += 4) {
-      const int ir = t / NCHA;
-      const int c = t - ir * NCHA;
-      const int slot = c * 64 + lane;      // 16B = half a pixel
-      const bf16_t* src =
-          ((slot >> 1) < Wi)
-              ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                      (long long)slot * 8)
-              : g_convp_zeros;
-      glds16_unseen(src, lds0 + img * IMG + ir * ARPB + c * 1024);
-    }
+    stage_rows<CI, NCHA, ARPB, true>(in, n, Hi, Wi, ho0, (nrows + 4) * NCHA,
+                                     wid, lane, lds0, img * IMG);
   };
 
   // packed results of one block, lane j = m & 3 of a quad, channels
@@ -900,12 +756,12 @@ void k_conv5_lds_nhwc(
   constexpr int CI = CIT;
   constexpr int nK = 25;                 // (kh, j), 5 chunks per tap row
   constexpr int CO = 16;
-  constexpr int AROW_BYTES = PIX * CI * 2;
-  constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
-  constexpr int ARPB = NCHA * 1024 + 64;
+  using Rows = RowImage<PIX, CI, true>;
+  constexpr int NCHA = Rows::NCH;
+  constexpr int ARPB = Rows::PITCH;
   constexpr int ROWS = 4;                // output rows per block
   constexpr int NROW = ROWS + 4;         // staged input rows
-  constexpr int MAXU = ((PIX - 4) / 16 + 3) / 4;  // units per wave
+  constexpr int MAXU = Rows::MAXU;       // units per wave
   __shared__ __attribute__((aligned(128))) char lds_all[NROW * ARPB];
 
   const int lane = threadIdx.x & 63;
@@ -926,8 +782,7 @@ void k_conv5_lds_nhwc(
   const long long n_blocks = (long long)Nn * hblocks;
   const int wg = blockIdx.x;
   const int n_wg = gridDim.x;
-  const unsigned lds0 =
-      (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_all;
+  const unsigned lds0 = lds_addr(lds_all);
 
   // UNPOOL staging. Staged row ir is real row ho0 + ir - 4 and staged
   // pixel pix is real pixel pix - 4, both even-aligned: the 8 rows are
@@ -1024,7 +879,7 @@ void k_conv5_lds_nhwc(
       if (PAD == 0) {
         src = (pix < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
                                sslot * 8)
-                         : g_convp_zeros;
+                         : conv5_zeros();
       } else {
         const int rrow = ho0 + ir - PAD;
         const int rpix = pix - PAD;
@@ -1034,13 +889,9 @@ void k_conv5_lds_nhwc(
         // sslot relative to the real pixel: subtract the border columns
         src = ok ? in + ((n * (Hi - 2 * PAD) + rrow) * (long long)rWi * CI +
                          (sslot - (long long)PAD * (CI / 8)) * 8)
-                 : g_convp_zeros;
+                 : conv5_zeros();
       }
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all + ir * ARPB +
-                                                    c * 1024),
-          16, 0, 0);
+      glds16(src, lds_all + ir * ARPB + c * 1024);
     }
     // (the pooled form has no LDS-DMA in flight here, and waiting would
     // also wait for the previous block's output stores)
@@ -1104,33 +955,16 @@ void k_conv5_lds_nhwc(
           for (int j = 0; j < 5; ++j) af[j] = afn[j];
         }
       }
-      // Lane (q, m) holds pixels q*4+i of channel m. A 4x4 transpose
-      // inside each lane quad (two DPP exchanges on packed bf16 pairs)
-      // gives it channels (m&~3)..+3 of pixel q*4+(m&3): one 8-byte
-      // store, 512 contiguous bytes per wave and row, in place of four
-      // 2-byte stores.
-      const unsigned sel1 = (m & 1) ? 0x03020706u : 0x05040100u;
-      const bool lo2 = (m & 3) < 2;
+      // Lane (q, m) holds pixels q*4+i of channel m. quad_tr4 gives it
+      // channels (m&~3)..+3 of pixel q*4+(m&3): one 8-byte store, 512
+      // contiguous bytes per wave and row, in place of four 2-byte
+      // stores.
 #pragma unroll
       for (int o = 0; o < ROWS; ++o) {
         unsigned v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = cf2bf(acc[o][i] + bias_v);
-        const unsigned a = v[0] | (v[1] << 16);
-        const unsigned b = v[2] | (v[3] << 16);
-        // lane^1: a1 / b1 pair element (m&1) / 2+(m&1) of both lanes
-        const unsigned a1 = __builtin_amdgcn_perm(
-            (unsigned)__builtin_amdgcn_mov_dpp((int)a, 0xB1, 0xF, 0xF, true),
-            a, sel1);
-        const unsigned b1 = __builtin_amdgcn_perm(
-            (unsigned)__builtin_amdgcn_mov_dpp((int)b, 0xB1, 0xF, 0xF, true),
-            b, sel1);
-        // lane^2: the lower lane pair keeps a1 and takes the upper
-        // pair's a1 as its channels 2..3; the upper pair mirrors it
-        const unsigned snd = lo2 ? b1 : a1;
-        const unsigned rcv =
-            (unsigned)__builtin_amdgcn_mov_dpp((int)snd, 0x4E, 0xF, 0xF, true);
-        pk[u][o] = make_uint2(lo2 ? a1 : rcv, lo2 ? rcv : b1);
+        pk[u][o] = quad_tr4(v[0], v[1], v[2], v[3], m);
       }
     }
     __syncthreads();
@@ -1228,8 +1062,7 @@ static int conv5_lds_launch(const bf16_t* in, const uint8_t* mask,
                             const bf16_t* w_frags, const float* bias,
                             bf16_t* out, int Nn, int Hi, int Wi, int Ho,
                             int Wo, int pad, int n_wg, hipStream_t s) {
-  const int W16 = (Wo + 15) >> 4;
-  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
+  const int need = conv5_stage_width(Wo, 16, Wi);
   if (need > 232 || (pad != 0 && pad != 4) || (mask && pad != 4)) return -1;
   const long long blocks = (long long)Nn * ((Ho + 3) / 4);
   if (n_wg <= 0) {
@@ -1278,8 +1111,7 @@ static int conv5_pool_launch(const bf16_t* in, const bf16_t* w_frags,
   const long long rows = (long long)Nn * (Ho >> 1);
   const long long blocks = (long long)Nn * (((Ho >> 1) + 1) >> 1);
   const dim3 block(CONV_THREADS);
-  const int W16 = (Wo + 15) >> 4;
-  const int need = W16 * 16 + 4 > Wi ? W16 * 16 + 4 : Wi;
+  const int need = conv5_stage_width(Wo, 16, Wi);
   auto grid_of = [&](long long cap) {
     long long g = n_wg > 0 ? n_wg : (blocks < cap ? blocks : cap);
     return dim3((unsigned)(g < 1 ? 1 : g));

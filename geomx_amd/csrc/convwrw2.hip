@@ -42,40 +42,17 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-
-#include "unpool.h"
-
-typedef unsigned short bf16_t;
-typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "conv5_common.h"
 
 #define WRW2_THREADS 256  // 4 waves
 #define WRW2_R 2          // gout rows per block
 
-__device__ __attribute__((aligned(64))) bf16_t g_wrw2_zeros[1024];
-
 // ds_read_b64_tr_b16: the 16-lane group covers one 4x16 bf16 row-major
 // tile (lane g supplies tile_base + g*8); lane g receives column g
-// (4 bf16, one per tile row). `a` is this lane's LDS byte address.
-__device__ __forceinline__ bf16x4 tr16_b64(unsigned a) {
-  bf16x4 d;
-  asm volatile("ds_read_b64_tr_b16 %0, %1"
-               : "=v"(d)
-               : "v"(a)
-               : "memory");
-  return d;
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3)))
-                               void*)p;
-}
-
-// The same read as a builtin: its result lands in MFMA operand registers
-// without a repack and the compiler counts its lgkmcnt wait, so reads can
-// stay in flight across MFMAs (both wrw kernels pipeline them this way).
+// (4 bf16, one per tile row). As a builtin its result lands in MFMA
+// operand registers without a repack and the compiler counts its lgkmcnt
+// wait, so reads can stay in flight across MFMAs (both wrw kernels
+// pipeline them this way). `p` is this lane's LDS address.
 __device__ __forceinline__ bf16x4 tr16_ld(
     const __attribute__((address_space(3))) char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
@@ -101,18 +78,18 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
   // with an all-ones A row (D[0][o] = sum_k B[k][o] accumulated over
   // every pixel window) — kills the separate at::native bias reduce
   constexpr int T16 = (NT + 1) * 16;
-  // row region: one 16-wide subimage row, padded to whole 1 KiB LDS-DMA
-  // chunks so every glds writes full 64-lane spans (no partial EXEC)
-  constexpr int ROW_BYTES = PIX * CI * 2;
-  constexpr int NCH = (ROW_BYTES + 1023) / 1024;       // glds chunks/row
-  constexpr int RPB = NCH * 1024;                      // region bytes
+  // row region: one 16-wide subimage row (input row, or one o-tile of a
+  // gout row), unskewed
+  using Rows = RowImage<PIX, CI, false>;
+  constexpr int NCH = Rows::NCH;                       // glds chunks/row
+  constexpr int RPB = Rows::PITCH;                     // region bytes
   constexpr int NROW_IN = WRW2_R + 4;
   constexpr int NROW_GO = WRW2_R * COT;
   // a gout row holds the WMAX * 32 pixels the K windows read, so the
   // last 1 KiB of its region is free; that of the last region holds the
   // bias tile's A image, 4 pixel rows of [1.0, 0 x 15] at +0 (k-pixels
   // 0..15) and at +512 (k-pixels 16..31)
-  constexpr int WMAX = (PIX - 4) / 32;   // K windows of a full row
+  constexpr int WMAX = Rows::WMAX;       // K windows of a full row
   constexpr int ONES = (NROW_IN + NROW_GO) * RPB - 1024;
   constexpr int ONES_BYTES = 512 + 128;
   static_assert(WMAX * 1024 + 1024 <= RPB, "room for the ones image");
@@ -172,22 +149,8 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
   auto stage_a = [&](long long n, int bh) {
     const int ho0 = bh * WRW2_R;
     const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
-    const int nchunks_a = (nrows + 4) * NCH;
-    for (int t = wid; t < nchunks_a; t += 4) {
-      const int ir = t / NCH;
-      const int c = t - ir * NCH;
-      const int slot = c * 64 + lane;              // 16B granule index
-      const int pix = slot >> 1;
-      const bf16_t* src =
-          (pix < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                             (long long)slot * 8)
-                     : g_wrw2_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all + ir * RPB +
-                                                    c * 1024),
-          16, 0, 0);
-    }
+    stage_rows<CI, NCH, RPB, false>(in, n, Hi, Wi, ho0, (nrows + 4) * NCH,
+                                    wid, lane, lds_all, 0);
   };
   // gout rows (full-resolution form): global [pix][CO] -> per-o-tile LDS
   // [pix][16], by LDS-DMA
@@ -207,61 +170,22 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
           (pix < Wo)
               ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
                         (long long)pix * CO + ot * 16 + half * 8)
-              : g_wrw2_zeros;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(lds_all +
-                                                    (NROW_IN + rr * COT +
-                                                     ot) * RPB +
-                                                    c * 1024),
-          16, 0, 0);
+              : conv5_zeros();
+      glds16(src, lds_all + (NROW_IN + rr * COT + ot) * RPB + c * 1024);
     }
   };
-  // UNPOOL: gout rows from the POOLED gradient + argmax mask (Ho, Wo
-  // even, so a block's 2 rows are pooled row bh): item `it` is one 16 B
-  // granule (8 channels) of pooled pixel wp, contiguous in global
-  // memory, and expands to its 4 full-resolution positions. Items past
-  // the row (wp >= Wo/2) write the zero tail [Wo, 32*W) the K windows
-  // read. The loads of the NEXT block wait in registers through this
-  // block's MFMA phase; the selects and ds_writes run after it.
+  // UNPOOL: gout rows from pooled row bh and its argmax codes
+  // (pooled_load / pooled_write of conv5_common.h; the selects and
+  // ds_writes run after the MFMA phase the loads fly through)
   constexpr int GV = CO / 8;
   constexpr int NIT = (16 * WMAX * GV + WRW2_THREADS - 1) / WRW2_THREADS;
   uint4 gq[NIT];
   uint2 mq[NIT];
   auto load_pooled = [&](long long n, int bh) {
-    const int nreal = (Wo >> 1) * GV;
-    const long long rowv = (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * GV;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int it = threadIdx.x + i * WRW2_THREADS;
-      gq[i] = make_uint4(0u, 0u, 0u, 0u);
-      mq[i] = make_uint2(~0u, ~0u);
-      if (it < nreal) {
-        gq[i] = reinterpret_cast<const uint4*>(gout)[rowv + it];
-        mq[i] = reinterpret_cast<const uint2*>(mask)[rowv + it];
-      }
-    }
+    pooled_load<NIT, WRW2_THREADS, GV>(gout, mask, n, bh, Ho, Wo, gq, mq);
   };
   auto write_pooled = [&]() {
-    const int nit = 16 * W * GV;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int it = threadIdx.x + i * WRW2_THREADS;
-      if (it < nit) {
-        const int wp = it / GV;
-        const int rem = it - wp * GV;
-        const int ot = rem >> 1;
-        const int half = rem & 1;
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx)
-            *reinterpret_cast<uint4*>(
-                lds_all + (NROW_IN + dy * COT + ot) * RPB +
-                (2 * wp + dx) * 32 + half * 16) =
-                unpool_select(gq[i], mq[i], dy * 2 + dx);
-      }
-    }
+    pooled_write<NIT, WRW2_THREADS, COT, 0, NROW_IN, RPB>(lds_all, W, gq, mq);
   };
 
   // ---- the (row, window) walk of one block. Fragment reads are
@@ -293,17 +217,11 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw16_nhwc(
     }
   };
   auto mma = [&](int j) __attribute__((always_inline)) {
-    union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
-    a.p.lo = afr[j][0];
-    a.p.hi = afr[j][1];
+    const bf16x8 a = join_bf16x4(afr[j][0], afr[j][1]);
 #pragma unroll
-    for (int ot = 0; ot < COT; ++ot) {
-      union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
-      b.p.lo = bcur[ot][0];
-      b.p.hi = bcur[ot][1];
+    for (int ot = 0; ot < COT; ++ot)
       acc[j][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          a.v, b.v, acc[j][ot], 0, 0, 0);
-    }
+          a, join_bf16x4(bcur[ot][0], bcur[ot][1]), acc[j][ot], 0, 0, 0);
   };
   // one step at offsets (oa, ob); (oa_n, ob_n) is the step after it
   auto step = [&](int oa, int ob, int oa_n, int ob_n, bool has_next)
@@ -493,28 +411,6 @@ __global__ void k_tr16_probe(const bf16_t* __restrict__ in,
 // barrier that ends it. The full-resolution form stages gout by LDS-DMA
 // into its single image between the two barriers.
 // ---------------------------------------------------------------------
-
-// One 1 KiB LDS-DMA piece (16 B per lane) that the compiler does not
-// see: for a __builtin_amdgcn_global_load_lds in flight hipcc puts
-// s_waitcnt vmcnt(0) ahead of the next LDS read it cannot prove
-// disjoint, which would end the prefetch of the NEXT block's image at
-// the first fragment read of this one. The kernel waits for its pieces
-// itself (vmcnt(0) ahead of the barrier that opens each MFMA phase).
-// `lds_dst` is the wave-uniform LDS byte address of the piece.
-__device__ __forceinline__ void glds16_unseen(const void* gsrc,
-                                              unsigned lds_dst) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
-      : "memory");
-}
-
 template <int PIX, bool UNPOOL = false>
 __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
     const bf16_t* __restrict__ in,    // [N][Hi][Wi][4]
@@ -527,16 +423,16 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
   constexpr int CO = 16;
   constexpr int NT = 7;                   // packed tap tiles, bias in T6
   constexpr int T16 = 176;                // slab rows (10 + 1 tiles)
-  constexpr int AROW_BYTES = PIX * CI * 2;
-  constexpr int NCHA = (AROW_BYTES + 1023) / 1024;
-  constexpr int ARPB = NCHA * 1024 + 64;  // 64B skew: distinct banks/row
-  constexpr int BROW_BYTES = PIX * 16 * 2;
-  constexpr int NCHB = (BROW_BYTES + 1023) / 1024;
-  constexpr int BRPB = NCHB * 1024;
+  using RowsA = RowImage<PIX, CI, true>;  // 64B skew: distinct banks/row
+  using RowsB = RowImage<PIX, CO, false>;
+  constexpr int NCHA = RowsA::NCH;
+  constexpr int ARPB = RowsA::PITCH;
+  constexpr int NCHB = RowsB::NCH;
+  constexpr int BRPB = RowsB::PITCH;
   constexpr int NROW_A = WRW2_R + 4;      // rows ho0 .. ho0+5
   constexpr int AIMG = NROW_A * ARPB;     // one A image; two of them
   constexpr int BOFF = 2 * AIMG;
-  constexpr int WMAX = (PIX - 4) / 32;    // K windows of a full row
+  constexpr int WMAX = RowsA::WMAX;       // K windows of a full row
   constexpr int ONES = BOFF + WRW2_R * BRPB;  // bf16 1.0, see ones_q
   constexpr int ONES_BYTES = WRW2_THREADS * 16;
   static_assert(AIMG % 128 == 0, "");
@@ -592,48 +488,27 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
   auto stage_a = [&](long long n, int bh, int img) {
     const int ho0 = bh * WRW2_R;
     const int nrows = (Ho - ho0) < WRW2_R ? (Ho - ho0) : WRW2_R;
-    const int nchunks_a = (nrows + 4) * NCHA;
-    for (int t = wid; t < nchunks_a; t += 4) {
-      const int ir = t / NCHA;
-      const int c = t - ir * NCHA;
-      const int slot = c * 64 + lane;              // 16B = 2 pixels
-      const int pix = slot * 2;
-      const bf16_t* src =
-          (pix + 1 < Wi) ? in + ((n * Hi + (ho0 + ir)) * (long long)Wi * CI +
-                                 (long long)pix * CI)
-                         : g_wrw2_zeros;
-      glds16_unseen(src, lds0 + img * AIMG + ir * ARPB + c * 1024);
-    }
+    stage_rows<CI, NCHA, ARPB, true>(in, n, Hi, Wi, ho0, (nrows + 4) * NCHA,
+                                     wid, lane, lds0, img * AIMG);
   };
   // UNPOOL: both gout rows of a block come from pooled row bh and its
-  // argmax codes (Ho, Wo even). Item `it` = threadIdx.x is one 16 B
-  // granule (8 channels) of pooled pixel it>>1 and expands to its 4
-  // full-resolution positions; items past the row write the zero tail
-  // [Wo, 32*W) the K windows read. At most one item per thread:
-  // 16 * 7 windows * 2 granules = 224.
-  static_assert(16 * ((PIX - 4) / 32) * 2 <= WRW2_THREADS, "");
-  uint4 gq = make_uint4(0u, 0u, 0u, 0u);
-  uint2 mq = make_uint2(~0u, ~0u);
+  // argmax codes (pooled_write, GV = 2). At most one item per thread:
+  // 16 * 7 windows * 2 granules = 224. The load stays here: it is
+  // pooled_load<1, .., 2> without the per-block reset of items past the
+  // row, and with the reset the kernel's registers change (96 -> 92
+  // VGPRs, 83 -> 87 SGPRs), so it would no longer be the measured kernel.
+  static_assert(16 * WMAX * 2 <= WRW2_THREADS, "");
+  uint4 gq[1] = {make_uint4(0u, 0u, 0u, 0u)};
+  uint2 mq[1] = {make_uint2(~0u, ~0u)};
   auto load_pooled = [&](long long n, int bh) {
     const long long rowv = (n * (Ho >> 1) + bh) * (long long)(Wo >> 1) * 2;
     if ((int)threadIdx.x < (Wo >> 1) * 2) {
-      gq = reinterpret_cast<const uint4*>(gout)[rowv + threadIdx.x];
-      mq = reinterpret_cast<const uint2*>(mask)[rowv + threadIdx.x];
+      gq[0] = reinterpret_cast<const uint4*>(gout)[rowv + threadIdx.x];
+      mq[0] = reinterpret_cast<const uint2*>(mask)[rowv + threadIdx.x];
     }
   };
   auto write_pooled = [&]() {
-    const int it = threadIdx.x;
-    if (it < 16 * W * 2) {
-      const int wp = it >> 1;
-      const int half = it & 1;
-#pragma unroll
-      for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx)
-          *reinterpret_cast<uint4*>(lds_all + BOFF + dy * BRPB +
-                                    (2 * wp + dx) * 32 + half * 16) =
-              unpool_select(gq, mq, dy * 2 + dx);
-    }
+    pooled_write<1, WRW2_THREADS, 1, BOFF, 0, BRPB>(lds_all, W, gq, mq);
   };
   auto stage_b = [&](long long n, int bh) {
     const int ho0 = bh * WRW2_R;
@@ -647,7 +522,7 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
       const bf16_t* src =
           (pix < Wo) ? gout + ((n * Ho + (ho0 + rr)) * (long long)Wo * CO +
                                (long long)slot * 8)
-                     : g_wrw2_zeros;
+                     : conv5_zeros();
       glds16_unseen(src, lds0 + BOFF + rr * BRPB + c * 1024);
     }
   };
@@ -712,17 +587,11 @@ __global__ __launch_bounds__(WRW2_THREADS) void k_conv5_wrw4_nhwc(
       f.a[1][1] = tr16_ld(ab1 + oa + 128);
     };
     auto mma = [&](const Frag& f) {
-      union { struct { bf16x4 lo, hi; } p; bf16x8 v; } b;
-      b.p.lo = f.b[0];
-      b.p.hi = f.b[1];
+      const bf16x8 b = join_bf16x4(f.b[0], f.b[1]);
 #pragma unroll
-      for (int j = 0; j < TPW; ++j) {
-        union { struct { bf16x4 lo, hi; } p; bf16x8 v; } a;
-        a.p.lo = f.a[j][0];
-        a.p.hi = f.a[j][1];
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc[j],
-                                                         0, 0, 0);
-      }
+      for (int j = 0; j < TPW; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            join_bf16x4(f.a[j][0], f.a[j][1]), b, acc[j], 0, 0, 0);
     };
     // The sched_barriers keep each step's reads ahead of the MFMAs they
     // overlap; the compiler places the counted lgkmcnt waits.
@@ -842,7 +711,7 @@ static int wrw16_launch(const bf16_t* in, const bf16_t* gout,
   if (CI != 16) return -1;
   if (mask && ((Ho | Wo) & 1)) return -1;
   const int W = (Wo + 31) >> 5;
-  const int need = (W * 32 + 4) > Wi ? (W * 32 + 4) : Wi;
+  const int need = conv5_stage_width(Wo, 32, Wi);
 #define W2KERNEL(COT_, PIX_, UNPOOL_, STRAIGHT_)                          \
   hipLaunchKernelGGL((k_conv5_wrw16_nhwc<COT_, PIX_, UNPOOL_, STRAIGHT_>), \
                      dim3(n_wg), dim3(WRW2_THREADS), 0, s, in, gout, part, \
@@ -876,8 +745,7 @@ static int wrw4_launch(const bf16_t* in, const bf16_t* gout,
   // Wi must be even: the A staging copies 2-pixel (16B) granules
   if (CI != 4 || CO != 16 || (Wi & 1)) return -1;
   if (mask && ((Ho | Wo) & 1)) return -1;
-  const int W = (Wo + 31) >> 5;
-  const int need = (W * 32 + 4) > Wi ? (W * 32 + 4) : Wi;
+  const int need = conv5_stage_width(Wo, 32, Wi);
 #define W4LAUNCH(PIX_)                                                    \
   if (need <= PIX_) {                                                     \
     if (mask)                                                             \
