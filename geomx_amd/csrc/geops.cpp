@@ -149,6 +149,20 @@ void check_f32(const torch::Tensor& t, const char* name) {
               " must be 16-byte aligned");
 }
 
+// the dense optimizer kernels take their length from w: g and every state
+// must hold as many elements, or the kernel reads and writes past them
+void check_same_numel(const torch::Tensor& w, const torch::Tensor& t,
+                      const char* name) {
+  TORCH_CHECK(t.numel() == w.numel(), name, " must have as many elements as w"
+              " (", t.numel(), " vs ", w.numel(), ")");
+}
+
+// Adam's bias-corrected rate at step t, in double
+double adam_lr_t(double lr, double beta1, double beta2, int64_t t) {
+  return lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) /
+         (1.0 - std::pow(beta1, (double)t));
+}
+
 void quantize_2bit(torch::Tensor grad, torch::Tensor residual,
                    torch::Tensor out, double thr) {
   check_f32(grad, "grad");
@@ -737,7 +751,7 @@ std::vector<torch::Tensor> conv5_pack_frags(torch::Tensor weight,
 void sgd_update(torch::Tensor w, torch::Tensor g, double lr, double wd,
                 double rescale) {
   check_f32(w, "w"); check_f32(g, "g");
-  TORCH_CHECK(w.numel() == g.numel());
+  check_same_numel(w, g, "g");
   geops_sgd_update(w.data_ptr<float>(), g.data_ptr<float>(), (float)lr,
                    (float)wd, (float)rescale, w.numel(), cur_stream());
   launch_check("sgd_update");
@@ -746,6 +760,7 @@ void sgd_update(torch::Tensor w, torch::Tensor g, double lr, double wd,
 void sgd_mom_update(torch::Tensor w, torch::Tensor g, torch::Tensor mom,
                     double lr, double momentum, double wd, double rescale) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(mom, "mom");
+  check_same_numel(w, g, "g"); check_same_numel(w, mom, "mom");
   geops_sgd_mom_update(w.data_ptr<float>(), g.data_ptr<float>(),
                        mom.data_ptr<float>(), (float)lr, (float)momentum,
                        (float)wd, (float)rescale, w.numel(), cur_stream());
@@ -756,9 +771,9 @@ void adam_update(torch::Tensor w, torch::Tensor g, torch::Tensor m,
                  torch::Tensor v, int64_t t, double lr, double beta1,
                  double beta2, double eps, double wd, double rescale) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(m, "m"); check_f32(v, "v");
-  const double lr_t =
-      lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) /
-      (1.0 - std::pow(beta1, (double)t));
+  check_same_numel(w, g, "g"); check_same_numel(w, m, "m");
+  check_same_numel(w, v, "v");
+  const double lr_t = adam_lr_t(lr, beta1, beta2, t);
   geops_adam_update(w.data_ptr<float>(), g.data_ptr<float>(),
                     m.data_ptr<float>(), v.data_ptr<float>(), (float)lr_t,
                     (float)beta1, (float)beta2, (float)eps, (float)wd,
@@ -772,6 +787,8 @@ void dcasgd_update(torch::Tensor w, torch::Tensor g, torch::Tensor prev_w,
   check_f32(w, "w"); check_f32(g, "g"); check_f32(prev_w, "prev_w");
   const bool has_mom = mom.defined() && mom.numel() > 0;
   if (has_mom) check_f32(mom, "mom");
+  check_same_numel(w, g, "g"); check_same_numel(w, prev_w, "prev_w");
+  if (has_mom) check_same_numel(w, mom, "mom");
   geops_dcasgd_update(w.data_ptr<float>(), g.data_ptr<float>(),
                       prev_w.data_ptr<float>(),
                       has_mom ? mom.data_ptr<float>() : nullptr, (float)lr,
@@ -784,6 +801,7 @@ void rmsprop_update(torch::Tensor w, torch::Tensor g, torch::Tensor n,
                     double lr, double rho, double eps, double wd,
                     double rescale) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(n, "n");
+  check_same_numel(w, g, "g"); check_same_numel(w, n, "n");
   geops_rmsprop_update(w.data_ptr<float>(), g.data_ptr<float>(),
                        n.data_ptr<float>(), (float)lr, (float)rho,
                        (float)eps, (float)wd, (float)rescale, w.numel(),
@@ -794,6 +812,7 @@ void rmsprop_update(torch::Tensor w, torch::Tensor g, torch::Tensor n,
 void adagrad_update(torch::Tensor w, torch::Tensor g, torch::Tensor h,
                     double lr, double eps, double wd, double rescale) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(h, "h");
+  check_same_numel(w, g, "g"); check_same_numel(w, h, "h");
   geops_adagrad_update(w.data_ptr<float>(), g.data_ptr<float>(),
                        h.data_ptr<float>(), (float)lr, (float)eps,
                        (float)wd, (float)rescale, w.numel(), cur_stream());
@@ -803,6 +822,7 @@ void adagrad_update(torch::Tensor w, torch::Tensor g, torch::Tensor h,
 void signsgd_update(torch::Tensor w, torch::Tensor g, double lr, double wd,
                     double rescale) {
   check_f32(w, "w"); check_f32(g, "g");
+  check_same_numel(w, g, "g");
   geops_signsgd_update(w.data_ptr<float>(), g.data_ptr<float>(), (float)lr,
                        (float)wd, (float)rescale, w.numel(), cur_stream());
   launch_check("signsgd_update");
@@ -811,6 +831,7 @@ void signsgd_update(torch::Tensor w, torch::Tensor g, double lr, double wd,
 void signum_update(torch::Tensor w, torch::Tensor g, torch::Tensor mom,
                    double lr, double momentum, double wd, double rescale) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(mom, "mom");
+  check_same_numel(w, g, "g"); check_same_numel(w, mom, "mom");
   geops_signum_update(w.data_ptr<float>(), g.data_ptr<float>(),
                       mom.data_ptr<float>(), (float)lr, (float)momentum,
                       (float)wd, (float)rescale, w.numel(), cur_stream());
@@ -914,9 +935,7 @@ void rsp_adam_update(torch::Tensor w, torch::Tensor ids, torch::Tensor merged,
                      double rescale) {
   check_rsp_rows(w, ids, merged);
   check_rsp_state(m, w, "m"); check_rsp_state(v, w, "v");
-  const double lr_t =
-      lr * std::sqrt(1.0 - std::pow(beta2, (double)t)) /
-      (1.0 - std::pow(beta1, (double)t));
+  const double lr_t = adam_lr_t(lr, beta1, beta2, t);
   geops_rsp_adam_update(i64p(ids), merged.data_ptr<float>(),
                         w.data_ptr<float>(), m.data_ptr<float>(),
                         v.data_ptr<float>(), (float)lr_t, (float)beta1,

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "optim_rules.h"
 
 #define GEOPS_THREADS 256
 #define GEOPS_MAX_BLOCKS 2048
@@ -686,29 +687,35 @@ extern "C" __global__ void k_dequantize_4bit(const uint8_t* __restrict__ in,
 
 // ---------------------------------------------------------------------------
 // Fused optimizer updates (the server ApplyUpdates hot loop,
-// optimizer_op.cc:43-651 semantics). fp32, float4-vectorized.
+// optimizer_op.cc:43-651 semantics). fp32. One loop over the rules of
+// optim_rules.h: VEC = 4 is float4 granules + scalar tail, VEC = 1 a plain
+// loop. blockDim.x in a device function keeps a partial-workgroup path that
+// a kernel body folds away, hence the builtin. k_signum_update and
+// k_dcasgd_update keep their own loops: through optim_dense they measured
+// 2.4 % and 6 % slower than before (docs/kernels.md).
 // ---------------------------------------------------------------------------
+
+template <int VEC, typename OP>
+__device__ __forceinline__ void optim_dense(
+    const OP& op, long long n, float* __restrict__ w,
+    const float* __restrict__ g, float* __restrict__ s0 = nullptr,
+    float* __restrict__ s1 = nullptr) {
+  const unsigned bdim = __builtin_amdgcn_workgroup_size_x();
+  const long long tid = (long long)blockIdx.x * bdim + threadIdx.x;
+  const long long stride = (long long)gridDim.x * bdim;
+  const long long nv = (VEC == 4) ? (n >> 2) : n;
+  for (long long i = tid; i < nv; i += stride)
+    optim_apply<VEC>(op, g + i * VEC, w, s0, s1, i * VEC);
+  if (VEC > 1)
+    for (long long i = nv * VEC + tid; i < n; i += stride)
+      optim_apply<1>(op, g + i, w, s0, s1, i);
+}
 
 extern "C" __global__ void k_sgd_update(float* __restrict__ w,
                                         const float* __restrict__ g,
                                         float lr, float wd, float rescale,
                                         long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long n4 = n >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  for (long long i = tid; i < n4; i += stride) {
-    float4 ww = w4[i];
-    const float4 gg = g4[i];
-    ww.x -= lr * (gg.x * rescale + wd * ww.x);
-    ww.y -= lr * (gg.y * rescale + wd * ww.y);
-    ww.z -= lr * (gg.z * rescale + wd * ww.z);
-    ww.w -= lr * (gg.w * rescale + wd * ww.w);
-    w4[i] = ww;
-  }
-  for (long long i = (n4 << 2) + tid; i < n; i += stride)
-    w[i] -= lr * (g[i] * rescale + wd * w[i]);
+  optim_dense<4>(SgdRule{lr, wd, rescale}, n, w, g);
 }
 
 extern "C" __global__ void k_sgd_mom_update(float* __restrict__ w,
@@ -717,26 +724,7 @@ extern "C" __global__ void k_sgd_mom_update(float* __restrict__ w,
                                             float lr, float momentum,
                                             float wd, float rescale,
                                             long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long n4 = n >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  float4* m4 = reinterpret_cast<float4*>(mom);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  for (long long i = tid; i < n4; i += stride) {
-    float4 ww = w4[i], mm = m4[i];
-    const float4 gg = g4[i];
-    mm.x = mm.x * momentum - lr * (gg.x * rescale + wd * ww.x); ww.x += mm.x;
-    mm.y = mm.y * momentum - lr * (gg.y * rescale + wd * ww.y); ww.y += mm.y;
-    mm.z = mm.z * momentum - lr * (gg.z * rescale + wd * ww.z); ww.z += mm.z;
-    mm.w = mm.w * momentum - lr * (gg.w * rescale + wd * ww.w); ww.w += mm.w;
-    w4[i] = ww; m4[i] = mm;
-  }
-  for (long long i = (n4 << 2) + tid; i < n; i += stride) {
-    const float mm = mom[i] * momentum - lr * (g[i] * rescale + wd * w[i]);
-    mom[i] = mm;
-    w[i] += mm;
-  }
+  optim_dense<4>(SgdMomRule{lr, momentum, wd, rescale}, n, w, g, mom);
 }
 
 extern "C" __global__ void k_adam_update(float* __restrict__ w,
@@ -746,35 +734,8 @@ extern "C" __global__ void k_adam_update(float* __restrict__ w,
                                          float lr_t, float beta1, float beta2,
                                          float eps, float wd, float rescale,
                                          long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long n4 = n >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-#define ADAM1(c)                                              \
-  {                                                           \
-    const float gg = gv.c * rescale + wd * wv.c;              \
-    mv.c = beta1 * mv.c + (1.0f - beta1) * gg;                \
-    vv.c = beta2 * vv.c + (1.0f - beta2) * gg * gg;           \
-    wv.c -= lr_t * mv.c / (sqrtf(vv.c) + eps);                \
-  }
-  for (long long i = tid; i < n4; i += stride) {
-    float4 wv = w4[i], mv = m4[i], vv = v4[i];
-    const float4 gv = g4[i];
-    ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-    w4[i] = wv; m4[i] = mv; v4[i] = vv;
-  }
-#undef ADAM1
-  for (long long i = (n4 << 2) + tid; i < n; i += stride) {
-    const float gg = g[i] * rescale + wd * w[i];
-    const float mm = beta1 * m[i] + (1.0f - beta1) * gg;
-    const float vv = beta2 * v[i] + (1.0f - beta2) * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    w[i] -= lr_t * mm / (sqrtf(vv) + eps);
-  }
+  optim_dense<4>(AdamRule{lr_t, beta1, beta2, eps, wd, rescale}, n, w, g, m,
+                 v);
 }
 
 extern "C" __global__ void k_rmsprop_update(float* __restrict__ w,
@@ -783,31 +744,7 @@ extern "C" __global__ void k_rmsprop_update(float* __restrict__ w,
                                             float lr, float rho, float eps,
                                             float wd, float rescale,
                                             long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long n4 = n >> 2;
-  float4* w4 = reinterpret_cast<float4*>(w);
-  float4* s4 = reinterpret_cast<float4*>(n_st);
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-#define RMS1(c)                                            \
-  {                                                        \
-    const float gg = gv.c * rescale + wd * wv.c;           \
-    sv.c = rho * sv.c + (1.0f - rho) * gg * gg;            \
-    wv.c -= lr * gg / (sqrtf(sv.c) + eps);                 \
-  }
-  for (long long i = tid; i < n4; i += stride) {
-    float4 wv = w4[i], sv = s4[i];
-    const float4 gv = g4[i];
-    RMS1(x) RMS1(y) RMS1(z) RMS1(w)
-    w4[i] = wv; s4[i] = sv;
-  }
-#undef RMS1
-  for (long long i = (n4 << 2) + tid; i < n; i += stride) {
-    const float gg = g[i] * rescale + wd * w[i];
-    const float sv = rho * n_st[i] + (1.0f - rho) * gg * gg;
-    n_st[i] = sv;
-    w[i] -= lr * gg / (sqrtf(sv) + eps);
-  }
+  optim_dense<4>(RmspropRule{lr, rho, eps, wd, rescale}, n, w, g, n_st);
 }
 
 extern "C" __global__ void k_adagrad_update(float* __restrict__ w,
@@ -815,26 +752,14 @@ extern "C" __global__ void k_adagrad_update(float* __restrict__ w,
                                             float* __restrict__ h,
                                             float lr, float eps, float wd,
                                             float rescale, long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = tid; i < n; i += stride) {
-    const float gg = g[i] * rescale + wd * w[i];
-    const float hv = h[i] + gg * gg;
-    h[i] = hv;
-    w[i] -= lr * gg / (sqrtf(hv) + eps);
-  }
+  optim_dense<1>(AdagradRule{lr, eps, wd, rescale}, n, w, g, h);
 }
 
 extern "C" __global__ void k_signsgd_update(float* __restrict__ w,
                                             const float* __restrict__ g,
                                             float lr, float wd,
                                             float rescale, long long n) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = tid; i < n; i += stride) {
-    const float gg = g[i] * rescale + wd * w[i];
-    w[i] -= lr * ((gg > 0.0f) ? 1.0f : ((gg < 0.0f) ? -1.0f : 0.0f));
-  }
+  optim_dense<1>(SignsgdRule{lr, wd, rescale}, n, w, g);
 }
 
 extern "C" __global__ void k_signum_update(float* __restrict__ w,

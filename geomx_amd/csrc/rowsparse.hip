@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "optim_rules.h"
 
 #define RSP_THREADS 256
 #define RSP_MAX_BLOCKS 2048
@@ -30,23 +31,6 @@ static inline int rsp_blocks(long long work) {
   if (b > RSP_MAX_BLOCKS) b = RSP_MAX_BLOCKS;
   return (int)b;
 }
-
-template <int VEC> struct RspGranule;
-template <> struct RspGranule<1> {
-  float v[1];
-  __device__ __forceinline__ void load(const float* p) { v[0] = p[0]; }
-  __device__ __forceinline__ void store(float* p) const { p[0] = v[0]; }
-};
-template <> struct RspGranule<4> {
-  float v[4];
-  __device__ __forceinline__ void load(const float* p) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  __device__ __forceinline__ void store(float* p) const {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
 
 // ---------------------------------------------------------------------------
 // rsp_merge: sum duplicate rows, deterministically and without atomics.
@@ -80,10 +64,10 @@ __global__ __launch_bounds__(RSP_THREADS) void k_rsp_merge(
     const long long c = (t - p * G) * VEC;
     const long long u = seg[p];
     if (p > 0 && seg[p - 1] == u) continue;  // not a segment head
-    RspGranule<VEC> acc;
+    Granule<VEC> acc;
     acc.load(vals + perm[p] * width + c);
     for (long long q = p + 1; q < nnz && seg[q] == u; ++q) {
-      RspGranule<VEC> x;
+      Granule<VEC> x;
       x.load(vals + perm[q] * width + c);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) acc.v[j] += x.v[j];
@@ -112,11 +96,11 @@ __global__ __launch_bounds__(RSP_THREADS) void k_rsp_scatter(
     const long long c = (t - u * G) * VEC;
     const long long r = ids[u];
     if (r < 0 || r >= rows) continue;
-    RspGranule<VEC> g;
+    Granule<VEC> g;
     g.load(merged + u * width + c);
     float* dst = dense + r * width + c;
     if (accumulate) {
-      RspGranule<VEC> d;
+      Granule<VEC> d;
       d.load(dst);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) g.v[j] = d.v[j] + g.v[j];
@@ -126,55 +110,12 @@ __global__ __launch_bounds__(RSP_THREADS) void k_rsp_scatter(
 }
 
 // ---------------------------------------------------------------------------
-// Row-indexed fused optimizer updates: the per-element arithmetic of
-// k_sgd_update / k_sgd_mom_update / k_adam_update / k_adagrad_update
-// (kernels.hip), same expressions in the same order, applied to row
-// ids[u] of w and of the state tensors with gradient row merged[u].
-// Rows that no id names are never read or written (lazy update).
+// Row-indexed fused optimizer updates: a rule of optim_rules.h (the functor
+// of that optimizer's dense kernel) on row ids[u] of w and of the states with
+// gradient row merged[u]; rows no id names are never touched (lazy update).
+// Own loads and stores, not optim_apply: through the helper the 16 B Adam
+// instantiation fuses the other product of its moments (docs/kernels.md).
 // ---------------------------------------------------------------------------
-struct RspSgd {
-  float lr, wd, rescale;
-  static constexpr int NSTATE = 0;
-  __device__ __forceinline__ void apply(float& w, float g, float&,
-                                        float&) const {
-    w -= lr * (g * rescale + wd * w);
-  }
-};
-
-struct RspSgdMom {
-  float lr, momentum, wd, rescale;
-  static constexpr int NSTATE = 1;
-  __device__ __forceinline__ void apply(float& w, float g, float& mom,
-                                        float&) const {
-    mom = mom * momentum - lr * (g * rescale + wd * w);
-    w += mom;
-  }
-};
-
-struct RspAdam {
-  float lr_t, beta1, beta2, eps, wd, rescale;
-  static constexpr int NSTATE = 2;
-  __device__ __forceinline__ void apply(float& w, float g, float& m,
-                                        float& v) const {
-    const float gg = g * rescale + wd * w;
-    m = beta1 * m + (1.0f - beta1) * gg;
-    v = beta2 * v + (1.0f - beta2) * gg * gg;
-    w -= lr_t * m / (sqrtf(v) + eps);
-  }
-};
-
-struct RspAdagrad {
-  float lr, eps, wd, rescale;
-  static constexpr int NSTATE = 1;
-  __device__ __forceinline__ void apply(float& w, float g, float& h,
-                                        float&) const {
-    const float gg = g * rescale + wd * w;
-    const float hv = h + gg * gg;
-    h = hv;
-    w -= lr * gg / (sqrtf(hv) + eps);
-  }
-};
-
 template <typename OP, int VEC>
 __global__ __launch_bounds__(RSP_THREADS) void k_rsp_update(
     OP op, const long long* __restrict__ ids,
@@ -191,7 +132,7 @@ __global__ __launch_bounds__(RSP_THREADS) void k_rsp_update(
     const long long r = ids[u];
     if (r < 0 || r >= rows) continue;
     const long long off = r * width + c;
-    RspGranule<VEC> g, wv, a, b;
+    Granule<VEC> g, wv, a, b;
     g.load(merged + u * width + c);
     wv.load(w + off);
     if (OP::NSTATE >= 1) a.load(s0 + off);
@@ -268,7 +209,7 @@ void geops_rsp_sgd_update(const long long* ids, const float* merged,
                           float* w, float lr, float wd, float rescale,
                           long long n_u, long long rows, long long width,
                           hipStream_t s) {
-  rsp_launch_update(RspSgd{lr, wd, rescale}, ids, merged, w, nullptr,
+  rsp_launch_update(SgdRule{lr, wd, rescale}, ids, merged, w, nullptr,
                     nullptr, n_u, rows, width, s);
 }
 
@@ -277,7 +218,7 @@ void geops_rsp_sgd_mom_update(const long long* ids, const float* merged,
                               float wd, float rescale, long long n_u,
                               long long rows, long long width,
                               hipStream_t s) {
-  rsp_launch_update(RspSgdMom{lr, momentum, wd, rescale}, ids, merged, w,
+  rsp_launch_update(SgdMomRule{lr, momentum, wd, rescale}, ids, merged, w,
                     mom, nullptr, n_u, rows, width, s);
 }
 
@@ -286,7 +227,7 @@ void geops_rsp_adam_update(const long long* ids, const float* merged,
                            float beta1, float beta2, float eps, float wd,
                            float rescale, long long n_u, long long rows,
                            long long width, hipStream_t s) {
-  rsp_launch_update(RspAdam{lr_t, beta1, beta2, eps, wd, rescale}, ids,
+  rsp_launch_update(AdamRule{lr_t, beta1, beta2, eps, wd, rescale}, ids,
                     merged, w, m, v, n_u, rows, width, s);
 }
 
@@ -295,7 +236,7 @@ void geops_rsp_adagrad_update(const long long* ids, const float* merged,
                               float wd, float rescale, long long n_u,
                               long long rows, long long width,
                               hipStream_t s) {
-  rsp_launch_update(RspAdagrad{lr, eps, wd, rescale}, ids, merged, w, h,
+  rsp_launch_update(AdagradRule{lr, eps, wd, rescale}, ids, merged, w, h,
                     nullptr, n_u, rows, width, s);
 }
 

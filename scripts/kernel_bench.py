@@ -137,6 +137,26 @@ def main():
                                              0.0, 1.0), args.iters)
     report("dcasgd_update", n * 4 * 5, sec)
 
+    sec = timeit(lambda: geops.dcasgd_update(w, g, pw, m, 0.01, 0.04, 0.9,
+                                             0.0, 1.0), args.iters)
+    report("dcasgd_update(mom)", n * 4 * 7, sec)
+
+    sec = timeit(lambda: geops.rmsprop_update(w, g, vv, 0.01, 0.9, 1e-8, 0.0,
+                                              1.0), args.iters)
+    report("rmsprop_update", n * 4 * 5, sec)
+
+    sec = timeit(lambda: geops.adagrad_update(w, g, vv, 0.01, 1e-7, 0.0, 1.0),
+                 args.iters)
+    report("adagrad_update", n * 4 * 5, sec)
+
+    sec = timeit(lambda: geops.signsgd_update(w, g, 0.01, 0.0, 1.0),
+                 args.iters)
+    report("signsgd_update", n * 4 * 3, sec)
+
+    sec = timeit(lambda: geops.signum_update(w, g, m, 0.01, 0.9, 0.0, 1.0),
+                 args.iters)
+    report("signum_update", n * 4 * 5, sec)
+
     if args.json_out:
         with open(args.json_out, "w") as f:
             json.dump({"n": n, "iters": args.iters, "results": results}, f,

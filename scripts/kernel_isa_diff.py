@@ -1,19 +1,25 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 code of every conv kernel between a base revision
-and the working tree, without a GPU.
+"""Compare the gfx950 code of every kernel of some source files between a
+base revision and the working tree, without a GPU.
 
-    python scripts/kernel_isa_diff.py BASE_REV [--diff] [--keep DIR]
+    python scripts/kernel_isa_diff.py BASE_REV [--files F.hip ...]
+                                      [--pair OLD=NEW ...] [--diff]
+                                      [--keep DIR]
 
 The sources under geomx_amd/csrc are taken from BASE_REV with `git show`
-into a temporary directory; conv.hip and convwrw2.hip of both sides are
-compiled to device-only assembly with the flags of setup.py. Per kernel
-the script compares
+into a temporary directory; the files (default: conv.hip and convwrw2.hip)
+of both sides are compiled to device-only assembly with the flags of
+setup.py. --pair names a kernel of the base and the one that replaced it,
+as the table prints them (`k<A, 4>=k<B, 4>`), so that a renamed template
+instantiation is compared with its predecessor instead of being listed
+twice as missing. Per kernel the script compares
 
   * the instruction stream: comments, directives and blank lines dropped,
     local labels and referenced data symbols renamed in order of first
     appearance (their numbering and names carry no code), and
   * the metadata the code object records: VGPR, AGPR, SGPR counts, LDS
-    and scratch bytes, spill counts
+    and scratch bytes, spill counts, and the occupancy the compiler
+    reports
 
 and prints one table row per kernel. --diff adds the unified diff of the
 two streams for every kernel whose stream differs. It only compares two
@@ -36,7 +42,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
 META = [("vgpr", "vgpr_count"), ("agpr", "agpr_count"),
         ("sgpr", "sgpr_count"), ("lds", "group_segment_fixed_size"),
         ("scratch", "private_segment_fixed_size"),
-        ("vspill", "vgpr_spill_count"), ("sspill", "sgpr_spill_count")]
+        ("vspill", "vgpr_spill_count"), ("sspill", "sgpr_spill_count"),
+        ("occ", "occupancy")]
 
 
 def hipcc():
@@ -58,9 +65,9 @@ def base_tree(rev, dst):
             f.write(blob)
 
 
-def compile_asm(cc, src_dir, out_dir):
+def compile_asm(cc, files, src_dir, out_dir):
     procs = []
-    for f in FILES:
+    for f in files:
         out = os.path.join(out_dir, f + ".s")
         procs.append((out, subprocess.Popen(
             [cc, *FLAGS, "-I", src_dir, "-o", out,
@@ -76,14 +83,18 @@ def parse(path):
     lines = open(path).read().splitlines()
     kernels = {m.group(1) for l in lines
                if (m := re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l))}
-    streams, cur = {}, None
+    streams, cur, occ, last = {}, None, {}, None
     for l in lines:
         code = l.split(";", 1)[0].strip()
         if not code:
+            m = re.match(r"\s*;\s*Occupancy:\s*(\d+)", l)
+            if m and last:
+                occ[last] = m.group(1)
             continue
         if cur is None:
             if code.endswith(":") and code[:-1] in kernels:
-                cur = streams.setdefault(code[:-1], [])
+                last = code[:-1]
+                cur = streams.setdefault(last, [])
             continue
         if code.startswith(".Lfunc_end"):
             cur = None
@@ -99,7 +110,9 @@ def parse(path):
                 meta[m.group(2).strip("'\"")] = cur_m
             else:
                 cur_m[m.group(1)] = m.group(2)
-    return {k: (normalise(streams[k]), meta.get(k, {})) for k in streams}
+    for k in streams:
+        meta.setdefault(k, {})["occupancy"] = occ.get(k, "?")
+    return {k: (normalise(streams[k]), meta[k]) for k in streams}
 
 
 def normalise(stream):
@@ -168,6 +181,12 @@ def short(name):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("base_rev")
+    ap.add_argument("--files", nargs="+", default=FILES, metavar="F.hip",
+                    help="sources under %s to compare (default: %s)"
+                    % (CSRC, " ".join(FILES)))
+    ap.add_argument("--pair", action="append", default=[],
+                    metavar="OLD=NEW",
+                    help="compare base kernel OLD with new kernel NEW")
     ap.add_argument("--diff", action="store_true",
                     help="print the stream diff of every kernel that differs")
     ap.add_argument("--keep", metavar="DIR",
@@ -186,7 +205,7 @@ def main():
                 os.makedirs(src, exist_ok=True)
                 base_tree(args.base_rev, src)
             sides[side] = {}
-            for s in compile_asm(cc, src, d):
+            for s in compile_asm(cc, args.files, src, d):
                 sides[side].update(parse(s))
     finally:
         if not args.keep:
@@ -194,6 +213,13 @@ def main():
 
     base, new = sides["base"], sides["new"]
     names = demangle(sorted(set(base) | set(new)))
+    by_short = {short(v): k for k, v in names.items()}
+    for pair in args.pair:
+        old, _, repl = pair.partition("=")
+        if by_short.get(old) not in base or by_short.get(repl) not in new:
+            sys.exit(f"--pair {pair}: no such kernel on that side")
+        base[by_short[repl]] = base.pop(by_short[old])
+        del names[by_short[old]]
     head = ["kernel", "instr base/new", "same"] + [h for h, _ in META]
     rows, diffs, all_same = [], [], True
     for k in sorted(names, key=lambda k: short(names[k])):

@@ -530,6 +530,31 @@ def test_noncontiguous_inplace_operand_raises(name):
             assert torch.equal(bad[k], keep[k])
 
 
+@pytest.mark.parametrize("n", [64, 63])
+@pytest.mark.parametrize("name", ["sgd", "sgd_mom", "adam", "rmsprop",
+                                  "adagrad", "signsgd", "signum",
+                                  "dcasgd_mom"])
+def test_short_operand_raises(name, n):
+    """g and every state one element short of w: the kernels take their
+    length from w, so this is an error naming the argument, raised before
+    any launch, and nothing is modified."""
+    st, g, hp = _opt_args(name, n)
+    for key in ["g"] + K.OPT_STATES[name]:
+        bad = {k: v.clone() for k, v in st.items()}
+        bad_g = g.clone()
+        if key == "g":
+            bad_g = bad_g[:n - 1]
+        else:
+            bad[key] = bad[key][:n - 1]
+        keep = {k: v.clone() for k, v in bad.items()}
+        with pytest.raises(RuntimeError,
+                           match="^" + key + " must have as many elements as w"):
+            K.opt_call(ops, name, bad, bad_g, hp)
+        for k in bad:
+            assert torch.equal(bad[k], keep[k])
+        assert torch.equal(bad_g, g[:bad_g.numel()])
+
+
 def test_noncontiguous_residual_and_out_raise():
     n = 64
     wide = torch.zeros(n, 2, device=DEV)
