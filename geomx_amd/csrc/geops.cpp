@@ -1,6 +1,7 @@
 // Torch bindings for the geomx_amd gfx950 kernel library: kernels.hip
 // (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
-// (5x5 conv forward / data gradient), convwrw2.hip (5x5 conv weight
+// (5x5 conv forward / data gradient), wirereduce.hip (fused decode-and-sum
+// of all parties' wire payloads), convwrw2.hip (5x5 conv weight
 // gradient, tr16 probes) and fc.hip (NHWC-native first dense layer
 // layout kernels: permuting weight casts, transposing flatten).
 //
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 // C-ABI launchers from the .hip files
 extern "C" {
@@ -55,6 +57,14 @@ void geops_signsgd_update(float*, const float*, float, float, float,
                           long long, hipStream_t);
 void geops_signum_update(float*, const float*, float*, float, float, float,
                          float, long long, hipStream_t);
+// wirereduce.hip
+void geops_wire_sum_2bit(const void* const*, int, float*, long long, float,
+                         bool, hipStream_t);
+void geops_wire_sum_f16(const void* const*, int, float*, long long, bool,
+                        hipStream_t);
+void geops_wire_sum_dgt(const float* const*, const int* const*,
+                        const uint8_t* const*, const float* const*, int,
+                        float*, long long, int, int, int, bool, hipStream_t);
 // rowsparse.hip
 void geops_rsp_merge(const long long*, const long long*, const long long*,
                      const float*, long long*, float*, long long, long long,
@@ -307,6 +317,98 @@ void dequantize_4bit(torch::Tensor packed, torch::Tensor minmax,
                         out.data_ptr<float>(), out.numel(), (int)chunk,
                         cur_stream());
   launch_check("dequantize_4bit");
+}
+
+// ---------------------------------------------------------------------------
+// Fused wire reduce (wirereduce.hip): out = (accumulate ? out : +0) + the
+// decoded payloads of all parties, folded in list order.
+// ---------------------------------------------------------------------------
+
+// one party's wire tensor: on out's device, contiguous, dtype and length
+// as the format prescribes. An empty tensor may have a null data pointer;
+// the kernels never dereference it.
+const void* check_payload(const torch::Tensor& t, const torch::Tensor& out,
+                          torch::ScalarType dtype, int64_t numel,
+                          const char* name, size_t party) {
+  TORCH_CHECK(t.is_cuda() && t.device() == out.device(), name, "[", party,
+              "] must be a GPU tensor on out's device");
+  TORCH_CHECK(t.is_contiguous(), name, "[", party, "] must be contiguous");
+  TORCH_CHECK(t.scalar_type() == dtype, name, "[", party, "] must be ",
+              dtype, ", got ", t.scalar_type());
+  TORCH_CHECK(t.numel() == numel, name, "[", party, "] must have ", numel,
+              " elements, got ", t.numel());
+  return t.data_ptr();
+}
+
+void wire_sum_2bit(std::vector<torch::Tensor> payloads, torch::Tensor out,
+                   double thr, bool accumulate) {
+  check_f32(out, "out");
+  TORCH_CHECK(!payloads.empty(), "wire_sum_2bit needs at least one party");
+  const long long n = out.numel();
+  std::vector<const void*> ptrs;
+  for (size_t p = 0; p < payloads.size(); ++p)
+    ptrs.push_back(check_payload(payloads[p], out, torch::kInt32,
+                                 (n + 15) / 16, "payloads", p));
+  geops_wire_sum_2bit(ptrs.data(), (int)ptrs.size(), out.data_ptr<float>(), n,
+                      (float)thr, accumulate, cur_stream());
+  launch_check("wire_sum_2bit");
+}
+
+void wire_sum_f16(std::vector<torch::Tensor> payloads, torch::Tensor out,
+                  bool accumulate) {
+  check_f32(out, "out");
+  TORCH_CHECK(!payloads.empty(), "wire_sum_f16 needs at least one party");
+  const long long n = out.numel();
+  std::vector<const void*> ptrs;
+  for (size_t p = 0; p < payloads.size(); ++p)
+    ptrs.push_back(check_payload(payloads[p], out, torch::kFloat16, n,
+                                 "payloads", p));
+  geops_wire_sum_f16(ptrs.data(), (int)ptrs.size(), out.data_ptr<float>(), n,
+                     accumulate, cur_stream());
+  launch_check("wire_sum_f16");
+}
+
+void wire_sum_dgt(std::vector<torch::Tensor> exacts,
+                  std::vector<torch::Tensor> keep_idxs,
+                  std::vector<torch::Tensor> packeds,
+                  std::vector<torch::Tensor> minmaxs, torch::Tensor out,
+                  int64_t chunk, bool accumulate) {
+  check_f32(out, "out");
+  const size_t P = exacts.size();
+  TORCH_CHECK(P >= 1, "wire_sum_dgt needs at least one party");
+  TORCH_CHECK(keep_idxs.size() == P && packeds.size() == P &&
+              minmaxs.size() == P,
+              "wire_sum_dgt needs the four payload lists equally long");
+  TORCH_CHECK(chunk >= 64 && chunk <= (1 << 30) && (chunk & (chunk - 1)) == 0,
+              "wire_sum_dgt needs a power-of-two chunk >= 64, got ", chunk);
+  const long long numel = out.numel();
+  const long long nchunks = (numel + chunk - 1) / chunk;
+  TORCH_CHECK(nchunks <= INT32_MAX, "too many chunks");
+  const long long n_keep = keep_idxs[0].numel();
+  TORCH_CHECK(n_keep <= nchunks, "keep_idx names ", n_keep, " of ", nchunks,
+              " chunks");
+  const long long n_lossy = nchunks - n_keep;
+  std::vector<const float*> pe, pm;
+  std::vector<const int*> pk;
+  std::vector<const uint8_t*> pp;
+  for (size_t p = 0; p < P; ++p) {
+    pe.push_back((const float*)check_payload(
+        exacts[p], out, torch::kFloat32, n_keep * chunk, "exact", p));
+    pk.push_back((const int*)check_payload(
+        keep_idxs[p], out, torch::kInt32, n_keep, "keep_idx", p));
+    pp.push_back((const uint8_t*)check_payload(
+        packeds[p], out, torch::kUInt8, n_lossy * (chunk / 2), "packed", p));
+    pm.push_back((const float*)check_payload(
+        minmaxs[p], out, torch::kFloat32, 2 * n_lossy, "minmax", p));
+    TORCH_CHECK(((uintptr_t)pe.back() & 15) == 0, "exact[", p,
+                "] must be 16-byte aligned");
+    TORCH_CHECK(((uintptr_t)pp.back() & 1) == 0, "packed[", p,
+                "] must be 2-byte aligned");
+  }
+  geops_wire_sum_dgt(pe.data(), pk.data(), pp.data(), pm.data(), (int)P,
+                     out.data_ptr<float>(), numel, (int)chunk, (int)nchunks,
+                     (int)n_keep, accumulate, cur_stream());
+  launch_check("wire_sum_dgt");
 }
 
 void relu_maxpool2_fwd(torch::Tensor in, torch::Tensor out, torch::Tensor idx,
@@ -970,6 +1072,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dgt_contribution", &dgt_contribution);
   m.def("quantize_4bit", &quantize_4bit);
   m.def("dequantize_4bit", &dequantize_4bit);
+  m.def("wire_sum_2bit", &wire_sum_2bit);
+  m.def("wire_sum_f16", &wire_sum_f16);
+  m.def("wire_sum_dgt", &wire_sum_dgt);
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
   m.def("conv5_pack_frags", &conv5_pack_frags, py::arg("weight"),

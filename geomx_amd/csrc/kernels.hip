@@ -16,6 +16,7 @@
 
 #include <cstdint>
 #include "optim_rules.h"
+#include "wire_codec.h"
 
 #define GEOPS_THREADS 256
 #define GEOPS_MAX_BLOCKS 2048
@@ -31,18 +32,9 @@ static inline int geops_blocks(long long work, int per_thread = 1) {
 // ---------------------------------------------------------------------------
 // 2bit quantization (gradient_compression-inl.h:40-139 semantics)
 // code: 0b11 -> +thr, 0b10 -> -thr, 0b00 -> 0; 16 codes per uint32 word,
-// slot s occupies bits [2s, 2s+1].
+// slot s occupies bits [2s, 2s+1]. spread16 and decode2 live in
+// wire_codec.h, shared with the fused wire reduce.
 // ---------------------------------------------------------------------------
-
-// spread 16 bits of x to even bit positions of a 32-bit word
-__device__ __forceinline__ uint32_t spread16(uint32_t x) {
-  x &= 0x0000FFFFu;
-  x = (x | (x << 8)) & 0x00FF00FFu;
-  x = (x | (x << 4)) & 0x0F0F0F0Fu;
-  x = (x | (x << 2)) & 0x33333333u;
-  x = (x | (x << 1)) & 0x55555555u;
-  return x;
-}
 
 extern "C" __global__ void k_quantize_2bit(const float* __restrict__ grad,
                                            float* __restrict__ residual,
@@ -76,10 +68,6 @@ extern "C" __global__ void k_quantize_2bit(const float* __restrict__ grad,
       if (w * 16 < n) out[w] = spread16(s0) | (spread16(s1) << 1);
     }
   }
-}
-
-__device__ __forceinline__ float decode2(uint32_t c, float thr) {
-  return (c == 3u) ? thr : ((c == 2u) ? -thr : 0.0f);
 }
 
 // vectorized main body: each thread decodes 4 elements (one byte of a
@@ -666,22 +654,22 @@ extern "C" __global__ void k_dequantize_4bit(const uint8_t* __restrict__ in,
   for (long long q = tid; q < nq; q += stride) {
     const int c = (int)((q << 2) >> log2c);
     const float lo = minmax[2 * c];
-    const float step = fmaxf(minmax[2 * c + 1] - lo, 1e-30f) / 16.0f;
+    const float step = step4(lo, minmax[2 * c + 1]);
     const uint16_t w = in16[q];
     float4 o;
-    o.x = lo + ((float)(w & 0xF) + 0.5f) * step;
-    o.y = lo + ((float)((w >> 4) & 0xF) + 0.5f) * step;
-    o.z = lo + ((float)((w >> 8) & 0xF) + 0.5f) * step;
-    o.w = lo + ((float)((w >> 12) & 0xF) + 0.5f) * step;
+    o.x = decode4(w & 0xF, lo, step);
+    o.y = decode4((w >> 4) & 0xF, lo, step);
+    o.z = decode4((w >> 8) & 0xF, lo, step);
+    o.w = decode4((w >> 12) & 0xF, lo, step);
     out4[q] = o;
   }
   for (long long i = (nq << 2) + tid; i < n; i += stride) {
     const int c = (int)(i >> log2c);
     const float lo = minmax[2 * c];
-    const float step = fmaxf(minmax[2 * c + 1] - lo, 1e-30f) / 16.0f;
+    const float step = step4(lo, minmax[2 * c + 1]);
     const uint8_t byte = in[i >> 1];
     const int code = (i & 1) ? (byte >> 4) : (byte & 0x0F);
-    out[i] = lo + ((float)code + 0.5f) * step;
+    out[i] = decode4(code, lo, step);
   }
 }
 

@@ -545,12 +545,7 @@ class KVStoreDist(KVStoreBase):
             work.wait()
         if kind == "2bit" and isinstance(payload, list):
             if self.topo.is_leader:
-                acc = torch.zeros(st.numel, device=self._device)
-                tmp = torch.empty(st.numel, device=self._device)
-                for p in payload:
-                    ops.dequantize_2bit(p, st.numel, extra, out=tmp)
-                    acc += tmp
-                return acc
+                return ops.wire_sum_2bit(payload, st.numel, extra)
             return payload[0].new_zeros(st.numel, dtype=torch.float32) \
                 if payload else torch.zeros(st.numel, device=self._device)
         return payload
@@ -578,13 +573,18 @@ class KVStoreDist(KVStoreBase):
                               party_sum: torch.Tensor) -> Optional[List[torch.Tensor]]:
         """Leader-tier exchange. Returns the list of per-party
         contributions on ranks that must apply the update (owner in
-        sharded mode / all leaders in replicated), else None."""
+        sharded mode / all leaders in replicated), else None. The dense
+        wire formats (2bit, fp16, DGT mode 3) return their fused sum as a
+        one-element list, except where dist_async applies every party's
+        contribution as an update of its own."""
         topo = self.topo
         P = topo.num_parties
         group = topo.leader_group
         ctype = self._effective_ctype(st)
         ratio = float(self.compression.get("threshold", self.cfg.bsc_ratio)) \
             if self.compression else self.cfg.bsc_ratio
+        per_party = self.cfg.mode == "dist_async" \
+            and self.optimizer is not None
 
         if ctype in ("bsc", "bsc_dgt"):
             if st.bsc_u is None:
@@ -636,10 +636,10 @@ class KVStoreDist(KVStoreBase):
             comm.all_gather(plist, packed, group=group)
             self.wan.charge(cross_party_bytes("all_gather",
                                               packed.numel() * 4, P))
-            dense = []
-            for p_ in plist:
-                dense.append(ops.dequantize_2bit(p_, st.numel, thr))
-            return dense
+            if per_party:
+                return [ops.dequantize_2bit(p_, st.numel, thr)
+                        for p_ in plist]
+            return [ops.wire_sum_2bit(plist, st.numel, thr)]
 
         if ctype == "fp16":
             if self._ts is not None:
@@ -651,7 +651,9 @@ class KVStoreDist(KVStoreBase):
             hlist = [torch.empty_like(h) for _ in range(P)]
             comm.all_gather(hlist, h, group=group)
             self.wan.charge(cross_party_bytes("all_gather", h.numel() * 2, P))
-            return [x.float() for x in hlist]
+            if per_party:
+                return [x.float() for x in hlist]
+            return [ops.wire_sum_fp16(hlist)]
 
         if ctype == "dgt":
             dg = self._dgt_state(st, party_sum.device)
@@ -666,8 +668,11 @@ class KVStoreDist(KVStoreBase):
                     comm.all_gather(lst, t, group=group)
                 self.wan.charge(cross_party_bytes(
                     "all_gather", dg.wire_bytes(), P))
-                return [dg.decompress(*(lst[p] for lst in gathered))
-                        for p in range(P)]
+                if per_party:
+                    return [dg.decompress(*(lst[p] for lst in gathered))
+                            for p in range(P)]
+                return [ops.wire_sum_dgt(list(zip(*gathered)), st.numel,
+                                         dg.chunk)]
             # modes 1/2: unimportant chunks travel exact (priority-only
             # semantics; no byte saving exists on a reliable fabric)
             contrib_now, wire = dg.transform(party_sum)

@@ -269,6 +269,62 @@ def dequantize_4bit_chunked(packed: torch.Tensor, minmax: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# Wire reduce: decode every party's payload and sum them in one kernel.
+#   out = (out if accumulate else +0) + c_0 + c_1 + ... + c_{P-1}
+# fp32, folded in list order: bit-equal to `acc = zeros; acc += decode(p)`.
+# ---------------------------------------------------------------------------
+
+def wire_sum_2bit(payloads, n: int, threshold: float,
+                  out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False) -> torch.Tensor:
+    """Sum of the 2bit payloads (packed int32 words) of all parties."""
+    if _on_gpu(out, *payloads):
+        g = _require_native()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32,
+                              device=payloads[0].device)
+            accumulate = False
+        g.wire_sum_2bit(list(payloads), _flat_inplace(out, "out"), threshold,
+                        accumulate)
+        return out
+    return ref.wire_sum_2bit(payloads, n, threshold, out, accumulate)
+
+
+def wire_sum_fp16(payloads, out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False) -> torch.Tensor:
+    """Sum of the fp16 wire tensors of all parties, in fp32."""
+    if _on_gpu(out, *payloads):
+        g = _require_native()
+        if out is None:
+            out = torch.empty(payloads[0].numel(), dtype=torch.float32,
+                              device=payloads[0].device)
+            accumulate = False
+        g.wire_sum_f16([p.reshape(-1) for p in payloads],
+                       _flat_inplace(out, "out"), accumulate)
+        return out
+    return ref.wire_sum_fp16(payloads, out, accumulate)
+
+
+def wire_sum_dgt(payloads, numel: int, chunk_elems: int,
+                 out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    """Sum of the DGT mode-3 payloads of all parties. Each payload is the
+    tuple of DGTState.compress: (exact, keep_idx, packed, minmax)."""
+    if _on_gpu(out, *(t for p in payloads for t in p)):
+        g = _require_native()
+        if out is None:
+            out = torch.empty(numel, dtype=torch.float32,
+                              device=payloads[0][0].device)
+            accumulate = False
+        exacts, keeps, packeds, minmaxs = (list(x) for x in zip(*payloads))
+        g.wire_sum_dgt(exacts, keeps, packeds,
+                       [m.reshape(-1) for m in minmaxs],
+                       _flat_inplace(out, "out"), chunk_elems, accumulate)
+        return out
+    return ref.wire_sum_dgt(payloads, numel, chunk_elems, out, accumulate)
+
+
+# ---------------------------------------------------------------------------
 # Fused optimizer updates
 # ---------------------------------------------------------------------------
 

@@ -244,6 +244,75 @@ def dequantize_4bit(packed: torch.Tensor, n: int, lo: float, hi: float
 
 
 # ---------------------------------------------------------------------------
+# Wire reduce: decode every party's payload and sum, in party order.
+#   out = (out if accumulate else +0) + c_0 + c_1 + ... + c_{P-1}
+# These are the op sequences the receive sites ran before the fused kernels
+# (zeros or `out`, then decode and `+=` per party), so they define the bits.
+# ---------------------------------------------------------------------------
+
+def _wire_acc(n: int, device, out: Optional[torch.Tensor],
+              accumulate: bool) -> torch.Tensor:
+    if out is None:
+        return torch.zeros(n, dtype=torch.float32, device=device)
+    acc = out.reshape(-1)
+    if not accumulate:
+        acc.zero_()
+    return acc
+
+
+def wire_sum_2bit(payloads, n: int, threshold: float,
+                  out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False) -> torch.Tensor:
+    acc = _wire_acc(n, payloads[0].device, out, accumulate)
+    tmp = torch.empty(n, dtype=torch.float32, device=acc.device)
+    for p in payloads:
+        dequantize_2bit(p, n, threshold, out=tmp)
+        acc += tmp
+    return acc if out is None else out
+
+
+def wire_sum_fp16(payloads, out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False) -> torch.Tensor:
+    acc = _wire_acc(payloads[0].numel(), payloads[0].device, out, accumulate)
+    for p in payloads:
+        acc += p.reshape(-1).float()
+    return acc if out is None else out
+
+
+def dgt_decompress(exact: torch.Tensor, keep_idx: torch.Tensor,
+                   packed: torch.Tensor, minmax: torch.Tensor, numel: int,
+                   chunk: int) -> torch.Tensor:
+    """Dense tensor of one DGT mode-3 wire payload (DGTState.compress):
+    kept chunks from `exact`, the others from their 4-bit codes."""
+    nchunks = (numel + chunk - 1) // chunk
+    n_keep = keep_idx.numel()
+    n_lossy = nchunks - n_keep
+    keep_mask = torch.zeros(nchunks, dtype=torch.bool, device=exact.device)
+    keep_mask[keep_idx.long()] = True
+    lossy_idx = (~keep_mask).nonzero(as_tuple=True)[0]
+    dense = torch.zeros(nchunks, chunk, device=exact.device)
+    if n_lossy:
+        half = chunk // 2
+        mm = minmax.view(n_lossy, 2)
+        dense[lossy_idx] = torch.stack([
+            dequantize_4bit(packed[c * half:(c + 1) * half], chunk,
+                            mm[c, 0].item(), mm[c, 1].item())
+            for c in range(n_lossy)])
+    dense[keep_idx.long()] = exact.view(n_keep, chunk)
+    return dense.reshape(-1)[:numel]
+
+
+def wire_sum_dgt(payloads, numel: int, chunk_elems: int,
+                 out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    acc = _wire_acc(numel, payloads[0][0].device, out, accumulate)
+    for exact, keep_idx, packed, minmax in payloads:
+        acc += dgt_decompress(exact, keep_idx, packed, minmax, numel,
+                              chunk_elems)
+    return acc if out is None else out
+
+
+# ---------------------------------------------------------------------------
 # FP16 transmission helpers (fp32 master copy semantics)
 # ---------------------------------------------------------------------------
 

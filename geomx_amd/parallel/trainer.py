@@ -502,7 +502,7 @@ class GeoTrainer:
                                          mode=self.cfg.enable_dgt or 3)
                     if b.dgt.mode >= 3:
                         # real reduced wire: gather the 4-bit payload
-                        # tuples, decompress-sum on arrival
+                        # tuples, one fused decode-and-sum on arrival
                         payload = b.dgt.compress(b.flat)
                         gathered = [[torch.empty_like(t) for _ in range(P)]
                                     for t in payload]
@@ -510,11 +510,11 @@ class GeoTrainer:
                             comm.all_gather(lst, t, group=topo.leader_group)
                         self.wan.charge(cross_party_bytes(
                             "all_gather", b.dgt.wire_bytes(), P))
-                        acc = torch.zeros_like(b.flat)
-                        for p_ in range(P):
-                            acc += b.dgt.decompress(
-                                *(lst[p_] for lst in gathered))
-                        b.flat.copy_(acc)
+                        # b.flat is no input of the sum: payload was
+                        # made from it above
+                        ops.wire_sum_dgt(list(zip(*gathered)),
+                                         b.flat.numel(), b.dgt.chunk,
+                                         out=b.flat)
                     else:
                         lossy, wire = b.dgt.transform(b.flat)
                         b.flat.copy_(lossy)
@@ -525,7 +525,7 @@ class GeoTrainer:
                     # leader-tier 2bit with WAN-side error feedback
                     # (DataPushToGlobalServersCompressed,
                     # kvstore_dist_server.h:786): exchange packed words,
-                    # dequantize-sum each party's contribution
+                    # one fused dequantize-and-sum of all parties
                     if b.res2bit is None:
                         b.res2bit = torch.zeros_like(b.flat)
                     thr = self.cfg.threshold
@@ -534,12 +534,7 @@ class GeoTrainer:
                     comm.all_gather(plist, packed, group=topo.leader_group)
                     self.wan.charge(cross_party_bytes(
                         "all_gather", packed.numel() * 4, P))
-                    acc = torch.zeros_like(b.flat)
-                    tmp = torch.empty_like(b.flat)
-                    for p_ in plist:
-                        ops.dequantize_2bit(p_, b.flat.numel(), thr, out=tmp)
-                        acc += tmp
-                    b.flat.copy_(acc)
+                    ops.wire_sum_2bit(plist, b.flat.numel(), thr, out=b.flat)
                 elif ctype in ("fp16", "mpq"):
                     if self._ts is not None:
                         # TSEngine relay (charges per hop internally)

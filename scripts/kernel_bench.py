@@ -32,11 +32,102 @@ def timeit(fn, iters, warmup=10):
     return (time.perf_counter() - t0) / iters
 
 
+def median_pair(fn_a, fn_b, iters, reps=7):
+    """Median seconds per call of two alternatives, timed with device
+    events in `reps` alternating windows of `iters` calls each, after a
+    warm-up of both."""
+    def window(fn):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / iters
+    for fn in (fn_a, fn_b):
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(reps):
+        ta.append(window(fn_a))
+        tb.append(window(fn_b))
+    return sorted(ta)[reps // 2], sorted(tb)[reps // 2]
+
+
+def wire_reduce_rows(n, iters, report, results):
+    """Fused wire reduce against the chain of single-party ops it replaced
+    at the receive sites, P = 2 and 8. Bytes are those that must move:
+    every party's payload in, 4n out."""
+    from geomx_amd.kvstore.dgt import DGTState
+    dev = "cuda:0"
+    dst = torch.empty(n, device=dev)
+    iters = max(5, iters // 5)
+
+    def row(name, P, nbytes, fused, chain):
+        tf, tc = median_pair(fused, chain, iters)
+        report("%s P=%d" % (name, P), nbytes, tf)
+        results[-1].update(chain_ms=round(tc * 1e3, 4),
+                           speedup=round(tc / tf, 2))
+        print("%24s chain %8.3f ms, fused is %.2fx" % ("", tc * 1e3, tc / tf))
+
+    for P in (2, 8):
+        grads = [torch.randn(n, device=dev) for _ in range(P)]
+
+        # 2bit: trainer / kvstore leader chain
+        thr = 0.5
+        pl = [ops.quantize_2bit(g, torch.zeros_like(g), thr) for g in grads]
+
+        def chain_2bit():
+            acc = torch.zeros(n, device=dev)
+            tmp = torch.empty(n, device=dev)
+            for w in pl:
+                ops.dequantize_2bit(w, n, thr, out=tmp)
+                acc += tmp
+            dst.copy_(acc)
+        row("wire_sum_2bit", P, P * pl[0].numel() * 4 + n * 4,
+            lambda: ops.wire_sum_2bit(pl, n, thr, out=dst), chain_2bit)
+
+        # fp16: kvstore WAN chain (P casts, P - 1 out-of-place adds)
+        hl = [g.half() for g in grads]
+
+        def chain_f16():
+            contribs = [x.float() for x in hl]
+            agg = contribs[0]
+            for c in contribs[1:]:
+                agg = agg + c
+            return agg
+        row("wire_sum_fp16", P, P * n * 2 + n * 4,
+            lambda: ops.wire_sum_fp16(hl, out=dst), chain_f16)
+        del hl
+
+        # DGT mode 3, k = 0.5, chunk 1024: trainer chain
+        sts = [DGTState(n, dev, chunk_elems=1024, k=0.5, mode=3)
+               for _ in range(P)]
+        dl = [st.compress(g) for st, g in zip(sts, grads)]
+        for st in sts:
+            st.residual = None  # not needed to decompress
+
+        def chain_dgt():
+            acc = torch.zeros(n, device=dev)
+            for st, d in zip(sts, dl):
+                acc += st.decompress(*d)
+            dst.copy_(acc)
+        row("wire_sum_dgt(k=.5)", P,
+            sum(t.numel() * t.element_size() for d in dl for t in d) + n * 4,
+            lambda: ops.wire_sum_dgt(dl, n, 1024, out=dst), chain_dgt)
+        del grads, pl, dl, sts
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 26)  # 64M fp32 = 256 MB
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--json-out", type=str, default=None)
+    ap.add_argument("--only-wire", action="store_true",
+                    help="only the wire reduce rows")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     assert ops.native_available(), ops.native_error()
@@ -54,6 +145,17 @@ def main():
         results.append(line)
         print(f"{name:24s} {nbytes/1e6:10.1f} MB {sec*1e3:8.3f} ms "
               f"{gbs:8.1f} GB/s")
+
+    def dump():
+        if args.json_out:
+            with open(args.json_out, "w") as f:
+                json.dump({"n": n, "iters": args.iters, "results": results},
+                          f, indent=1)
+
+    if args.only_wire:
+        wire_reduce_rows(n, args.iters, report, results)
+        dump()
+        return
 
     # --- 2bit quantize: read g + r, write r + n/16 words
     r = torch.zeros(n, device=dev)
@@ -157,10 +259,10 @@ def main():
                  args.iters)
     report("signum_update", n * 4 * 5, sec)
 
-    if args.json_out:
-        with open(args.json_out, "w") as f:
-            json.dump({"n": n, "iters": args.iters, "results": results}, f,
-                      indent=1)
+    del w, m, vv, pw, u, v, g, r, out, p4
+    torch.cuda.empty_cache()
+    wire_reduce_rows(n, args.iters, report, results)
+    dump()
 
 
 if __name__ == "__main__":

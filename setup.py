@@ -7,12 +7,13 @@ GPU machines with the source snapshot.
 """
 
 import os
+import subprocess
 
 from setuptools import setup
 
 os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
 
-from torch.utils.cpp_extension import (BuildExtension,  # noqa: E402
+from torch.utils.cpp_extension import (ROCM_HOME, BuildExtension,  # noqa: E402
                                        CppExtension, CUDAExtension)
 
 here = os.path.dirname(os.path.abspath(__file__))
@@ -33,6 +34,40 @@ ext = CUDAExtension(
     },
 )
 
+# Kernel files built WITHOUT packed fp32 instructions (v_pk_add/mul/fma_f32):
+# their sums are specified one rounded addition at a time and are compiled
+# to scalar fp32 VALU ops only. The extension's flag list is one for all of
+# its sources, so these are compiled here, with the same flags plus the
+# feature switch, and linked into _geops as objects. They include no torch
+# header.
+NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip"]
+NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h"]
+NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+ext.depends += NO_PK_F32_SOURCES + NO_PK_F32_DEPENDS
+
+
+class GeoBuildExtension(BuildExtension):
+    def build_extension(self, ext_):
+        if ext_ is ext:
+            for src in NO_PK_F32_SOURCES:
+                obj = os.path.join(self.build_temp,
+                                   os.path.splitext(src)[0] + ".o")
+                os.makedirs(os.path.dirname(obj), exist_ok=True)
+                deps = [os.path.join(here, f)
+                        for f in [src] + NO_PK_F32_DEPENDS]
+                if not os.path.exists(obj) or any(
+                        os.path.getmtime(d) > os.path.getmtime(obj)
+                        for d in deps):
+                    subprocess.check_call(
+                        [os.path.join(ROCM_HOME, "bin", "hipcc"), "-O3",
+                         "-std=c++17", "--offload-arch=gfx950", "-fPIC"]
+                        + NO_PK_F32_FLAGS
+                        + ["-c", os.path.join(here, src), "-o", obj])
+                if obj not in ext_.extra_objects:
+                    ext_.extra_objects.append(obj)
+        super().build_extension(ext_)
+
+
 # host-side IO runtime (record-file reader) — plain C++, no HIP
 io_ext = CppExtension(
     name="geomx_amd._geoio",
@@ -46,5 +81,5 @@ setup(
     packages=["geomx_amd", "geomx_amd.kvstore", "geomx_amd.ops",
               "geomx_amd.parallel", "geomx_amd.models", "geomx_amd.utils"],
     ext_modules=[ext, io_ext],
-    cmdclass={"build_ext": BuildExtension},
+    cmdclass={"build_ext": GeoBuildExtension},
 )
