@@ -1,9 +1,10 @@
 // Torch bindings for the geomx_amd gfx950 kernel library: kernels.hip
 // (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
 // (5x5 conv forward / data gradient), wirereduce.hip (fused decode-and-sum
-// of all parties' wire payloads), convwrw2.hip (5x5 conv weight
-// gradient, tr16 probes) and fc.hip (NHWC-native first dense layer
-// layout kernels: permuting weight casts, transposing flatten).
+// of all parties' wire payloads), dgtencode.hip (fused DGT mode-3 encode),
+// convwrw2.hip (5x5 conv weight gradient, tr16 probes) and fc.hip
+// (NHWC-native first dense layer layout kernels: permuting weight casts,
+// transposing flatten).
 //
 // Thin checked wrappers: dtype/contiguity/device checks, stream plumbing
 // (kernels run on the current torch stream so they order correctly with
@@ -65,6 +66,9 @@ void geops_wire_sum_f16(const void* const*, int, float*, long long, bool,
 void geops_wire_sum_dgt(const float* const*, const int* const*,
                         const uint8_t* const*, const float* const*, int,
                         float*, long long, int, int, int, bool, hipStream_t);
+// dgtencode.hip
+int geops_dgt_encode(const float*, float*, const float*, const int*, float*,
+                     uint8_t*, float*, long long, int, int, int, hipStream_t);
 // rowsparse.hip
 void geops_rsp_merge(const long long*, const long long*, const long long*,
                      const float*, long long*, float*, long long, long long,
@@ -409,6 +413,51 @@ void wire_sum_dgt(std::vector<torch::Tensor> exacts,
                      out.data_ptr<float>(), numel, (int)chunk, (int)nchunks,
                      (int)n_keep, accumulate, cur_stream());
   launch_check("wire_sum_dgt");
+}
+
+// ---------------------------------------------------------------------------
+// Fused DGT encode (dgtencode.hip): the mode-3 wire payload of one bucket and
+// the residual update in one kernel. The outputs are written whole.
+// ---------------------------------------------------------------------------
+
+void dgt_encode(torch::Tensor x, torch::Tensor residual, torch::Tensor contrib,
+                torch::Tensor keep_idx, torch::Tensor exact,
+                torch::Tensor packed, torch::Tensor minmax, int64_t chunk) {
+  check_f32(x, "x"); check_f32(residual, "residual");
+  check_f32(exact, "exact");
+  TORCH_CHECK(chunk >= 64 && chunk <= 8192 && (chunk & (chunk - 1)) == 0,
+              "dgt_encode serves a power-of-two chunk in [64, 8192], got ",
+              chunk);
+  const long long numel = x.numel();
+  TORCH_CHECK(numel >= 1, "dgt_encode needs at least one element");
+  TORCH_CHECK(residual.numel() == numel, "residual must have as many "
+              "elements as x (", residual.numel(), " vs ", numel, ")");
+  const long long nchunks = (numel + chunk - 1) / chunk;
+  TORCH_CHECK(nchunks <= INT32_MAX, "too many chunks");
+  const long long n_keep = keep_idx.numel();
+  TORCH_CHECK(n_keep <= nchunks, "keep_idx names ", n_keep, " of ", nchunks,
+              " chunks");
+  const long long n_lossy = nchunks - n_keep;
+  check_payload(contrib, x, torch::kFloat32, nchunks, "contrib", 0);
+  check_payload(keep_idx, x, torch::kInt32, n_keep, "keep_idx", 0);
+  TORCH_CHECK(residual.device() == x.device() && exact.device() == x.device(),
+              "residual and exact must be on x's device");
+  TORCH_CHECK(exact.numel() == n_keep * chunk, "exact must have ",
+              n_keep * chunk, " elements, got ", exact.numel());
+  // empty when n_lossy == 0: the data pointers may be null, never used
+  const void* pk = check_payload(packed, x, torch::kUInt8,
+                                 n_lossy * (chunk / 2), "packed", 0);
+  const void* mm = check_payload(minmax, x, torch::kFloat32, 2 * n_lossy,
+                                 "minmax", 0);
+  TORCH_CHECK(((uintptr_t)pk & 15) == 0 && ((uintptr_t)mm & 15) == 0,
+              "packed and minmax must be 16-byte aligned");
+  const int rc = geops_dgt_encode(
+      x.data_ptr<float>(), residual.data_ptr<float>(),
+      contrib.data_ptr<float>(), keep_idx.data_ptr<int32_t>(),
+      exact.data_ptr<float>(), (uint8_t*)pk, (float*)mm, numel, (int)chunk,
+      (int)nchunks, (int)n_keep, cur_stream());
+  TORCH_CHECK(rc == 0, "dgt_encode: no kernel for chunk ", chunk);
+  launch_check("dgt_encode");
 }
 
 void relu_maxpool2_fwd(torch::Tensor in, torch::Tensor out, torch::Tensor idx,
@@ -1075,6 +1124,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wire_sum_2bit", &wire_sum_2bit);
   m.def("wire_sum_f16", &wire_sum_f16);
   m.def("wire_sum_dgt", &wire_sum_dgt);
+  m.def("dgt_encode", &dgt_encode);
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
   m.def("conv5_pack_frags", &conv5_pack_frags, py::arg("weight"),

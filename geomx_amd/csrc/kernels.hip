@@ -602,7 +602,7 @@ extern "C" __global__ void k_quantize_4bit(const float* __restrict__ x,
     // chunk is a power of two >= 4: the 4 elements of q share one chunk
     const int c = (int)((q << 2) >> log2c);
     const float lo = minmax[2 * c];
-    const float step = fmaxf(minmax[2 * c + 1] - lo, 1e-30f) / 16.0f;
+    const float step = step4(lo, minmax[2 * c + 1]);
     const float inv = 1.0f / step;
     const float4 xx = x4[q];
     float f[4] = {xx.x, xx.y, xx.z, xx.w};
@@ -614,9 +614,8 @@ extern "C" __global__ void k_quantize_4bit(const float* __restrict__ x,
     float rout[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      int code = (int)floorf((f[j] - lo) * inv);
-      code = code < 0 ? 0 : (code > 15 ? 15 : code);
-      rout[j] = f[j] - (lo + ((float)code + 0.5f) * step);
+      const uint32_t code = encode4(f[j], lo, inv);
+      rout[j] = f[j] - decode4(code, lo, step);
       word |= (uint16_t)(code << (4 * j));
     }
     if (has_res) r4[q] = make_float4(rout[0], rout[1], rout[2], rout[3]);

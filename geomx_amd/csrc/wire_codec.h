@@ -1,6 +1,6 @@
-// Wire codecs shared by the single-party kernels (kernels.hip) and the
-// fused wire reduce (wirereduce.hip): one definition of each decode, so
-// both sides produce the same bits.
+// Wire codecs shared by the single-party kernels (kernels.hip), the fused
+// wire reduce (wirereduce.hip) and the fused DGT encode (dgtencode.hip): one
+// definition of each encode and decode, so all of them produce the same bits.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,4 +39,10 @@ __device__ __forceinline__ float step4(float lo, float hi) {
 
 __device__ __forceinline__ float decode4(uint32_t code, float lo, float step) {
   return lo + ((float)code + 0.5f) * step;
+}
+
+// code of f on a chunk with minimum lo; inv = 1.0f / step4(lo, hi)
+__device__ __forceinline__ uint32_t encode4(float f, float lo, float inv) {
+  const int code = (int)floorf((f - lo) * inv);
+  return (uint32_t)(code < 0 ? 0 : (code > 15 ? 15 : code));
 }

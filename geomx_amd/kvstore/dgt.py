@@ -81,34 +81,11 @@ class DGTState:
         self._update_contrib(flat)
         keep_idx = torch.topk(self.contrib, self.n_keep).indices \
             .sort().values
-        dead = self.contrib == 0
-        pad = self.nchunks * self.chunk
-        if pad != self.numel:
-            fpad = torch.zeros(pad, device=flat.device)
-            fpad[:self.numel] = flat
-            rpad = torch.zeros(pad, device=flat.device)
-            rpad[:self.numel] = self.residual
-        else:
-            fpad, rpad = flat, self.residual
-        packed, minmax = ops.quantize_4bit_chunked(fpad, self.chunk, rpad)
-        minmax = minmax.to(flat.device)
-        if pad != self.numel:
-            self.residual.copy_(rpad[:self.numel])
-        # residual is only meaningful for quantized chunks
-        keep_mask = torch.zeros(self.nchunks, dtype=torch.bool,
-                                device=flat.device)
-        keep_mask[keep_idx] = True
-        elem_keep = keep_mask.repeat_interleave(self.chunk)[:self.numel]
-        self.residual[elem_keep] = 0.0
-
-        lossy_idx = (~keep_mask).nonzero(as_tuple=True)[0]
-        exact = fpad.view(self.nchunks, self.chunk)[keep_idx].clone()
-        exact[dead[keep_idx]] = 0.0
-        pk = packed.view(self.nchunks, self.chunk // 2)[lossy_idx] \
-            .reshape(-1).contiguous()
-        mm = minmax.view(self.nchunks, 2)[lossy_idx].clone()
-        mm[dead[lossy_idx]] = 0.0
-        return (exact.reshape(-1), keep_idx.to(torch.int32), pk, mm)
+        # exact rows, 4-bit rows, codebooks and the residual update (zero
+        # for kept chunks, quantization error for the rest): one kernel on
+        # the GPU, the op sequence of ops.reference.dgt_encode elsewhere
+        return ops.dgt_encode(flat, self.residual, self.contrib, keep_idx,
+                              self.chunk)
 
     def decompress(self, exact: torch.Tensor, keep_idx: torch.Tensor,
                    packed: torch.Tensor, minmax: torch.Tensor) -> torch.Tensor:

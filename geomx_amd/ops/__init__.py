@@ -268,6 +268,47 @@ def dequantize_4bit_chunked(packed: torch.Tensor, minmax: torch.Tensor,
     return full
 
 
+def _dgt_encode_served(x: torch.Tensor, residual: torch.Tensor,
+                       chunk_elems: int) -> bool:
+    """What k_dgt_encode serves: a power-of-two chunk in [64, 8192] and
+    contiguous fp32 operands on 16 B boundaries."""
+    return (64 <= chunk_elems <= 8192
+            and chunk_elems & (chunk_elems - 1) == 0
+            and x.numel() > 0
+            and all(t.dtype == torch.float32 and t.is_contiguous()
+                    and t.data_ptr() % 16 == 0 for t in (x, residual)))
+
+
+def dgt_encode(x: torch.Tensor, residual: torch.Tensor, contrib: torch.Tensor,
+               keep_idx: torch.Tensor, chunk_elems: int):
+    """DGT mode-3 wire payload of a bucket: (exact, keep_idx i32, packed,
+    minmax), the tuple of DGTState.compress. `residual` is updated in
+    place; `contrib` is the per-chunk EWMA (0 marks a dead chunk) and
+    `keep_idx` the sorted indices of the chunks that travel exact. On the
+    GPU one kernel writes the whole payload; a chunk size or operand
+    outside what it serves, and CPU tensors, take the op sequence of
+    ref.dgt_encode, whose bits the kernel reproduces."""
+    flat = x.reshape(-1)
+    if _on_gpu(flat, residual) \
+            and _dgt_encode_served(flat, residual, chunk_elems):
+        g = _require_native()
+        res = _flat_inplace(residual, "residual")
+        numel = flat.numel()
+        nchunks = (numel + chunk_elems - 1) // chunk_elems
+        keep32 = keep_idx.to(torch.int32).contiguous()
+        n_keep = keep32.numel()
+        n_lossy = nchunks - n_keep
+        dev = flat.device
+        exact = torch.empty(n_keep * chunk_elems, device=dev)
+        packed = torch.empty(n_lossy * (chunk_elems // 2), dtype=torch.uint8,
+                             device=dev)
+        minmax = torch.empty((n_lossy, 2), device=dev)
+        g.dgt_encode(flat, res, contrib.float().contiguous(), keep32, exact,
+                     packed, minmax.view(-1), chunk_elems)
+        return exact, keep32, packed, minmax
+    return ref.dgt_encode(x, residual, contrib, keep_idx, chunk_elems)
+
+
 # ---------------------------------------------------------------------------
 # Wire reduce: decode every party's payload and sum them in one kernel.
 #   out = (out if accumulate else +0) + c_0 + c_1 + ... + c_{P-1}

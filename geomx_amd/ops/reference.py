@@ -243,6 +243,48 @@ def dequantize_4bit(packed: torch.Tensor, n: int, lo: float, hi: float
     return lo + (codes + 0.5) * step
 
 
+def dgt_encode(x: torch.Tensor, residual: torch.Tensor, contrib: torch.Tensor,
+               keep_idx: torch.Tensor, chunk: int):
+    """DGT mode-3 wire payload (exact, keep_idx i32, packed, minmax) of a
+    flat bucket `x`; `residual` is updated in place. `contrib` is the
+    per-chunk EWMA (0 marks a dead chunk), `keep_idx` the sorted kept
+    chunks. This is the op sequence DGTState.compress ran before the fused
+    kernel, so it defines the bits: the 4-bit tier runs over zero-padded
+    whole chunks through the chunked quantize op of the tensors' device."""
+    from . import quantize_4bit_chunked  # the dispatching op, as compress did
+    flat = x.reshape(-1)
+    numel = flat.numel()
+    nchunks = (numel + chunk - 1) // chunk
+    dead = contrib == 0
+    keep_idx = keep_idx.long()  # topk gives int64; the wire form is int32
+    pad = nchunks * chunk
+    if pad != numel:
+        fpad = torch.zeros(pad, device=flat.device)
+        fpad[:numel] = flat
+        rpad = torch.zeros(pad, device=flat.device)
+        rpad[:numel] = residual
+    else:
+        fpad, rpad = flat, residual
+    packed, minmax = quantize_4bit_chunked(fpad, chunk, rpad)
+    minmax = minmax.to(flat.device)
+    if pad != numel:
+        residual.copy_(rpad[:numel])
+    # residual is only meaningful for quantized chunks
+    keep_mask = torch.zeros(nchunks, dtype=torch.bool, device=flat.device)
+    keep_mask[keep_idx] = True
+    elem_keep = keep_mask.repeat_interleave(chunk)[:numel]
+    residual[elem_keep] = 0.0
+
+    lossy_idx = (~keep_mask).nonzero(as_tuple=True)[0]
+    exact = fpad.view(nchunks, chunk)[keep_idx].clone()
+    exact[dead[keep_idx]] = 0.0
+    pk = packed.view(nchunks, chunk // 2)[lossy_idx] \
+        .reshape(-1).contiguous()
+    mm = minmax.view(nchunks, 2)[lossy_idx].clone()
+    mm[dead[lossy_idx]] = 0.0
+    return (exact.reshape(-1), keep_idx.to(torch.int32), pk, mm)
+
+
 # ---------------------------------------------------------------------------
 # Wire reduce: decode every party's payload and sum, in party order.
 #   out = (out if accumulate else +0) + c_0 + c_1 + ... + c_{P-1}

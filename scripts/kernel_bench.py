@@ -9,6 +9,7 @@ Prints one line per kernel: name, bytes moved per call, ms, GB/s.
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -32,10 +33,10 @@ def timeit(fn, iters, warmup=10):
     return (time.perf_counter() - t0) / iters
 
 
-def median_pair(fn_a, fn_b, iters, reps=7):
-    """Median seconds per call of two alternatives, timed with device
-    events in `reps` alternating windows of `iters` calls each, after a
-    warm-up of both."""
+def window_pair(fn_a, fn_b, iters, reps=7):
+    """Seconds per call of two alternatives in each of `reps` alternating
+    windows of `iters` calls, timed with device events, after a warm-up of
+    both."""
     def window(fn):
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
@@ -53,7 +54,47 @@ def median_pair(fn_a, fn_b, iters, reps=7):
     for _ in range(reps):
         ta.append(window(fn_a))
         tb.append(window(fn_b))
+    return ta, tb
+
+
+def median_pair(fn_a, fn_b, iters, reps=7):
+    """Median seconds per call of the two alternatives of window_pair."""
+    ta, tb = window_pair(fn_a, fn_b, iters, reps)
     return sorted(ta)[reps // 2], sorted(tb)[reps // 2]
+
+
+def dgt_encode_rows(n, iters, report, results):
+    """Fused DGT mode-3 encode against the op chain it replaced in
+    DGTState.compress (ref.dgt_encode on the GPU), chunk 1024, k = 0.5 and
+    0.25. Bytes are those that must move: x and the residual in, the
+    residual out, 4k bytes of exact rows and (1 - k) / 2 of codes per
+    element. The spread is (max - min) / median over the 7 windows."""
+    dev = "cuda:0"
+    chunk = 1024
+    iters = max(5, iters // 5)
+    x = torch.randn(n, device=dev)
+    contrib = ops.dgt_contribution(x, chunk)
+    for k in (0.5, 0.25):
+        n_keep = max(1, math.ceil(k * contrib.numel()))
+        keep_idx = torch.topk(contrib, n_keep).indices.sort().values
+        res_f = 0.05 * torch.randn(n, device=dev)
+        res_c = res_f.clone()
+        tf, tc = window_pair(
+            lambda: ops.dgt_encode(x, res_f, contrib, keep_idx, chunk),
+            lambda: ref.dgt_encode(x, res_c, contrib, keep_idx, chunk), iters)
+        mf, mc = sorted(tf)[len(tf) // 2], sorted(tc)[len(tc) // 2]
+        report("dgt_encode(k=%g)" % k,
+               int(8 * n + 4 * n + 4 * k * n + (1 - k) * n / 2), mf)
+        results[-1].update(chain_ms=round(mc * 1e3, 4),
+                           speedup=round(mc / mf, 2),
+                           spread=round((max(tf) - min(tf)) / mf, 3),
+                           chain_spread=round((max(tc) - min(tc)) / mc, 3))
+        print("%24s chain %8.3f ms, fused is %.2fx; spread between windows "
+              "%.1f%% fused, %.1f%% chain"
+              % ("", mc * 1e3, mc / mf, 100 * results[-1]["spread"],
+                 100 * results[-1]["chain_spread"]))
+        del res_f, res_c
+        torch.cuda.empty_cache()
 
 
 def wire_reduce_rows(n, iters, report, results):
@@ -128,6 +169,8 @@ def main():
     ap.add_argument("--json-out", type=str, default=None)
     ap.add_argument("--only-wire", action="store_true",
                     help="only the wire reduce rows")
+    ap.add_argument("--only-dgt", action="store_true",
+                    help="only the fused DGT encode rows")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     assert ops.native_available(), ops.native_error()
@@ -154,6 +197,11 @@ def main():
 
     if args.only_wire:
         wire_reduce_rows(n, args.iters, report, results)
+        dump()
+        return
+    if args.only_dgt:
+        del g
+        dgt_encode_rows(n, args.iters, report, results)
         dump()
         return
 
@@ -262,6 +310,7 @@ def main():
     del w, m, vv, pw, u, v, g, r, out, p4
     torch.cuda.empty_cache()
     wire_reduce_rows(n, args.iters, report, results)
+    dgt_encode_rows(n, args.iters, report, results)
     dump()
 
 

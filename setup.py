@@ -36,11 +36,14 @@ ext = CUDAExtension(
 
 # Kernel files built WITHOUT packed fp32 instructions (v_pk_add/mul/fma_f32):
 # their sums are specified one rounded addition at a time and are compiled
-# to scalar fp32 VALU ops only. The extension's flag list is one for all of
-# its sources, so these are compiled here, with the same flags plus the
-# feature switch, and linked into _geops as objects. They include no torch
-# header.
-NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip"]
+# to scalar fp32 VALU ops only. dgtencode.hip is kept to scalar fp32 ops in
+# the same way; there the switch changes no result, only registers (204
+# VGPRs with packed fp32 on against 156 at chunk 8192, docs/kernels.md).
+# The extension's flag list is one for all of its sources, so these are
+# compiled here, with the same flags plus the feature switch, and linked
+# into _geops as objects. They include no torch header.
+NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
+                     "geomx_amd/csrc/dgtencode.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h"]
 NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 ext.depends += NO_PK_F32_SOURCES + NO_PK_F32_DEPENDS
