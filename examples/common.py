@@ -36,6 +36,8 @@ def base_parser():
     p.add_argument("-sc", "--split-by-class", action="store_true")
     p.add_argument("--parties", type=int, default=1)
     p.add_argument("--image-size", type=int, default=28)
+    p.add_argument("--channels", type=int, default=3,
+                   help="input channels; 1 is the grayscale conv1 stage")
     p.add_argument("--data-n", type=int, default=1024)
     p.add_argument("--max-iters", type=int, default=0)
     p.add_argument("--measure-out", type=str, default=None)
@@ -54,7 +56,8 @@ def setup(args, mode="dist_sync", **cfg_overrides):
                 global_mode=getattr(args, "global_mode", "sharded"))
     device = topo.device
     torch.manual_seed(0)
-    net = geo_cnn(in_channels=3, image_size=args.image_size).to(device)
+    net = geo_cnn(in_channels=getattr(args, "channels", 3),
+                  image_size=args.image_size).to(device)
     return kv, net, device
 
 
@@ -63,7 +66,7 @@ def topo_world():
 
 
 def make_loaders(args, kv, device):
-    shape = (3, args.image_size, args.image_size)
+    shape = (getattr(args, "channels", 3), args.image_size, args.image_size)
     train = SyntheticImageDataset(args.data_n, shape=shape, seed=1)
     test = SyntheticImageDataset(256, shape=shape, seed=2)
     train_iter = worker_loader(train, args.batch_size, kv.num_all_workers,

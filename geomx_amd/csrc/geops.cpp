@@ -126,6 +126,11 @@ int geops_conv5_dgrad_nwg_nhwc(const unsigned short*, const uint8_t*,
                                const unsigned short*, unsigned short*, int,
                                int, int, int, int, int, int, int,
                                hipStream_t);
+int geops_conv5c1_pool(const void*, int, const unsigned short*, const float*,
+                       unsigned short*, uint8_t*, int, int, int, int,
+                       hipStream_t);
+int geops_conv5c1_wrw(const void*, int, const unsigned short*, const uint8_t*,
+                      float*, int, int, int, int, hipStream_t);
 int geops_fc_w_permute_bf16(const float*, unsigned short*, int, int, int,
                             hipStream_t);
 int geops_fc_w_unpermute_f32(const unsigned short*, float*, int, int, int,
@@ -717,6 +722,121 @@ void conv5_dgrad_nwg_nhwc(torch::Tensor in, torch::Tensor mask,
   launch_check("conv5_dgrad_nwg_nhwc");
 }
 
+// ---- grayscale conv1 stage (conv1c.hip): CI = 1, CO = 16 ----
+
+// x is the [N][1][H][W] tensor as it is, fp32 or bf16 (the kernels round
+// fp32 while staging). Returns 1 for fp32, 0 for bf16.
+int check_c1_input(const torch::Tensor& x, int64_t N, int64_t H, int64_t W,
+                   const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), what,
+              ": x must be a contiguous GPU tensor");
+  const bool f32 = x.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(f32 || x.scalar_type() == torch::kBFloat16, what,
+              ": x must be fp32 or bf16");
+  TORCH_CHECK(N >= 1 && H >= 5 && W >= 5 && x.numel() == N * H * W, what,
+              ": x does not hold N*H*W elements");
+  TORCH_CHECK(((uintptr_t)x.data_ptr() & (f32 ? 7 : 3)) == 0, what,
+              ": x must be aligned to a pixel pair");
+  return f32 ? 1 : 0;
+}
+
+// a dense NHWC operand: plain contiguous, or an NCHW-shaped channels_last
+void check_c1_nhwc(const torch::Tensor& t, torch::ScalarType dtype,
+                   int64_t numel, const char* what, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype, what, ": ", name,
+              " has the wrong device or dtype");
+  TORCH_CHECK(t.is_contiguous() ||
+                  (t.dim() == 4 &&
+                   t.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              what, ": ", name, " must be dense");
+  TORCH_CHECK(t.numel() == numel, what, ": ", name, " holds ", t.numel(),
+              " elements, expected ", numel);
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 15) == 0, what, ": ", name,
+              " must be 16-byte aligned");
+}
+
+// the grid: n_wg > 0 as given (test hook), 0 = min(cap, blocks)
+int64_t c1_grid(int64_t n_wg, int64_t blocks, int64_t cap, const char* what) {
+  TORCH_CHECK(n_wg >= 0 && n_wg <= 65536, what, ": bad n_wg");
+  if (n_wg > 0) return n_wg;
+  return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
+}
+
+// conv(1 -> 16, 5x5) + bias + ReLU + 2x2 max-pool; out / mask as
+// conv5_pool_nhwc. Blocks are 4 conv rows; the default grid is two
+// resident rounds, as for the CI = 4 kernel.
+void conv5c1_pool(torch::Tensor x, torch::Tensor w_frags, torch::Tensor bias,
+                  torch::Tensor out, torch::Tensor mask, int64_t N, int64_t H,
+                  int64_t W, int64_t n_wg) {
+  const char* what = "conv5c1_pool";
+  const int f32 = check_c1_input(x, N, H, W, what);
+  const int64_t Hop = (H - 4) / 2, Wop = (W - 4) / 2;
+  check_c1_nhwc(w_frags, torch::kBFloat16, 2 * 64 * 8, what, "w_frags");
+  check_c1_nhwc(out, torch::kBFloat16, N * Hop * Wop * 16, what, "out");
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 &&
+                  mask.is_contiguous() && mask.numel() == out.numel() &&
+                  ((uintptr_t)mask.data_ptr() & 3) == 0,
+              what, ": mask must be uint8, dense, as large as out");
+  const bool has_bias = bias.defined() && bias.numel() > 0;
+  if (has_bias)
+    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == torch::kFloat32 &&
+                    bias.is_contiguous() && bias.numel() == 16,
+                what, ": bias must be 16 fp32 values");
+  const int64_t grid = c1_grid(n_wg, N * ((Hop + 1) / 2), 2048, what);
+  const int rc = geops_conv5c1_pool(
+      x.data_ptr(), f32, (const unsigned short*)w_frags.data_ptr(),
+      has_bias ? bias.data_ptr<float>() : nullptr,
+      (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(), (int)N,
+      (int)H, (int)W, (int)grid, cur_stream());
+  TORCH_CHECK(rc == 0, what, ": unsupported geometry H=", H, " W=", W,
+              " (even H, even W in 6..228)");
+  launch_check(what);
+}
+
+void c1_wrw(const char* what, torch::Tensor x, torch::Tensor g,
+            const torch::Tensor* mask, torch::Tensor part, int64_t N,
+            int64_t H, int64_t W, int64_t n_wg) {
+  const int f32 = check_c1_input(x, N, H, W, what);
+  const int64_t Ho = H - 4, Wo = W - 4;
+  if (mask) {
+    check_c1_nhwc(g, torch::kBFloat16, N * (Ho / 2) * (Wo / 2) * 16, what,
+                  "gp");
+    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == torch::kUInt8 &&
+                    mask->is_contiguous() && mask->numel() == g.numel() &&
+                    ((uintptr_t)mask->data_ptr() & 7) == 0,
+                what, ": mask must be uint8, dense, as large as gp");
+  } else {
+    check_c1_nhwc(g, torch::kBFloat16, N * Ho * Wo * 16, what, "go");
+  }
+  const int64_t grid = c1_grid(n_wg, N * ((Ho + 1) / 2), 768, what);
+  check_f32(part, "part");
+  TORCH_CHECK(part.numel() == grid * 32 * 16, what, ": part must be [", grid,
+              "][32][16]");
+  const int rc = geops_conv5c1_wrw(
+      x.data_ptr(), f32, (const unsigned short*)g.data_ptr(),
+      mask ? mask->data_ptr<uint8_t>() : nullptr, part.data_ptr<float>(),
+      (int)N, (int)H, (int)W, (int)grid, cur_stream());
+  TORCH_CHECK(rc == 0, what, ": unsupported geometry H=", H, " W=", W,
+              " (even W in 6..228; even H for the pooled form)");
+  launch_check(what);
+}
+
+// Weight + bias gradient slabs part[n_wg][32][16] (rows 0..24 the taps
+// kh*5+kw, row 25 the bias, rows 26..31 zero) from the full-resolution
+// gradient go [N][Ho][Wo][16]; the default grid is min(768, N*ceil(Ho/2)).
+void conv5c1_wrw(torch::Tensor x, torch::Tensor go, torch::Tensor part,
+                 int64_t N, int64_t H, int64_t W, int64_t n_wg) {
+  c1_wrw("conv5c1_wrw", x, go, nullptr, part, N, H, W, n_wg);
+}
+
+// The same from the POOLED gradient gp [N][Ho/2][Wo/2][16] and its
+// argmax codes: the kernel unpools while staging.
+void conv5c1_wrw_unpool(torch::Tensor x, torch::Tensor gp, torch::Tensor mask,
+                        torch::Tensor part, int64_t N, int64_t H, int64_t W,
+                        int64_t n_wg) {
+  c1_wrw("conv5c1_wrw_unpool", x, gp, &mask, part, N, H, W, n_wg);
+}
+
 // ---- first dense layer layout kernels (fc.hip) ----
 
 void check_fc_operand(const torch::Tensor& t, torch::ScalarType dtype,
@@ -1135,6 +1255,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_direct_nhwc", &conv5_direct_nhwc);
   m.def("conv5_dgrad_nwg_nhwc", &conv5_dgrad_nwg_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
+  m.def("conv5c1_pool", &conv5c1_pool);
+  m.def("conv5c1_wrw", &conv5c1_wrw);
+  m.def("conv5c1_wrw_unpool", &conv5c1_wrw_unpool);
   m.def("conv5_pool_nwg_nhwc", &conv5_pool_nwg_nhwc);
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);

@@ -1,5 +1,6 @@
 """GeoConv5 / GeoConv5Pool: 5x5 stride-1 convolution stages on the
-hand-written gfx950 MFMA kernels (csrc/conv.hip, convwrw2.hip).
+hand-written gfx950 MFMA kernels (csrc/conv.hip, convwrw2.hip,
+conv1c.hip).
 
 Each of the three ops of a stage is routed on its own, from geometry
 alone (plan_conv5):
@@ -15,6 +16,10 @@ Behind a fused-pool forward the wrw and lds_pad4 kernels take the
 pooled gradient and the argmax mask as they are (unpool_fusable) and do
 the max-pool backward while staging; no full-resolution gradient is
 built unless another route needs it.
+A one-channel first layer (CIr = 1, CO = 16: the grayscale conv1 stage)
+has kernels of its own (conv1c.hip): forward 'pool1' and weight gradient
+'wrw1' read the [N][1][H][W] input as it is, fp32 or bf16, with no pad,
+cast or layout kernel in front; its data gradient stays on ATen.
 Whatever no kernel serves goes to ATen (same math, library kernels);
 one op on ATen does not move the other two off the custom kernels.
 """
@@ -33,6 +38,8 @@ _SUPPORTED_DGRAD = {(32, 16), (16, 16)}
 _POOL_SHAPES = {(4, 16), (16, 32), (16, 16)}
 _WRW_SHAPES = {(4, 16), (16, 32), (16, 16)}
 _WRW_NWG = 768  # partial slabs (3 workgroups per CU)
+_C1_SHAPE = (1, 16)   # (CIr, CO) of the grayscale conv1 stage
+_C1_MAXW = 228        # its kernels' row image: 14 tiles / 7 K windows + 4
 
 # shapes where the direct forward kernel MEASURES faster than MIOpen on
 # MI355X (conv1 3->16 @224px: 0.73 vs 1.63 ms). conv2-class shapes tie
@@ -83,6 +90,22 @@ def build_fwd_index(weight_shape) -> torch.Tensor:
         return ((o * CIr + ci) * KH + kh) * KW + kw
 
     return _frag_index(CO, CI, numel, entry)
+
+
+def build_c1_fwd_index(weight_shape) -> torch.Tensor:
+    """Gather table of k_conv5c1_pool's two B fragments, [2][64][8], for
+    a [16][1][5][5] weight: K-slot k = kh*8 + kw, so lane (q, n) of chunk
+    km holds w[n][0][4*km + q][0..4] and three dead slots; kh > 4 (chunk
+    1, q >= 1) is dead too. Dead slots index the zero element."""
+    CO, CIr, KH, KW = weight_shape
+    assert (CIr, CO, KH, KW) == _C1_SHAPE + (5, 5), weight_shape
+    km, lane, j = torch.meshgrid(torch.arange(2), torch.arange(64),
+                                 torch.arange(8), indexing="ij")
+    kh, n = km * 4 + (lane >> 4), lane & 15
+    live = (kh < KH) & (j < KW)
+    idx = torch.where(live, (n * KH + kh) * KW + j,
+                      torch.full_like(j, CO * KH * KW))
+    return idx.reshape(-1)
 
 
 def build_dgrad_index(weight_shape) -> torch.Tensor:
@@ -158,6 +181,24 @@ def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
     return dw
 
 
+def wrw1_via_kernel(x: torch.Tensor, go: torch.Tensor,
+                    mask: torch.Tensor = None):
+    """(dW [16][1][5][5], db [16]) in fp32 from k_conv5c1_wrw: x is the
+    [N][1][H][W] input, fp32 or bf16, read as it is; go the NHWC bf16
+    gradient, or with `mask` the pooled gradient and its argmax codes.
+    Slab rows 0..24 are the taps kh*5+kw, row 25 is the bias."""
+    from geomx_amd import _geops
+    N, _, H, W = x.shape
+    n_wg = min(_WRW_NWG, N * ((H - 4 + 1) // 2))
+    part = torch.empty(n_wg, 32, 16, dtype=torch.float32, device=x.device)
+    if mask is not None:
+        _geops.conv5c1_wrw_unpool(x, go, mask, part, N, H, W, 0)
+    else:
+        _geops.conv5c1_wrw(x, go, part, N, H, W, 0)
+    full = part.sum(dim=0)
+    return full[:25].T.reshape(16, 1, 5, 5), full[25]
+
+
 # ---------------------------------------------------------------------
 # routing
 # ---------------------------------------------------------------------
@@ -176,13 +217,13 @@ def plan_conv5(weight_shape, H: int, W: int, pooled: bool = False,
     """Route of each op of a 5x5 stride-1 pad-0 conv stage on an
     [N][CIr][H][W] input, from geometry alone:
 
-        fwd    'pool' | 'direct' | 'aten'
+        fwd    'pool' | 'pool1' | 'direct' | 'aten'
         dgrad  'lds_pad4' | 'direct_padded' | 'aten'
-        wrw    'wrw4' | 'wrw16' | 'aten'      (weight + bias gradient)
+        wrw    'wrw4' | 'wrw16' | 'wrw1' | 'aten'   (weight + bias gradient)
 
     The predicates restate the launch tables of geops_conv5_nhwc,
     geops_conv5_pool_nhwc (conv.hip) and geops_conv5_wrw{4,16}_nhwc
-    (convwrw2.hip): each LDS kernel is compiled for a fixed staging
+    (convwrw2.hip) and geops_conv5c1_{pool,wrw} (conv1c.hip): each LDS kernel is compiled for a fixed staging
     width and serves a row only while tiles*tile_width + 4 halo pixels
     fit in it. The bindings raise on anything outside those tables, so
     drift between this function and the launchers fails loudly."""
@@ -191,6 +232,14 @@ def plan_conv5(weight_shape, H: int, W: int, pooled: bool = False,
         return _ALL_ATEN
     CI = (CIr + 3) & ~3
     Ho, Wo = H - 4, W - 4
+
+    # the grayscale first layer: kernels of its own on the one-channel
+    # row image, even W up to 228; a first layer gets no dgrad kernel
+    if (CIr, CO) == _C1_SHAPE:
+        if W % 2 or not 6 <= W <= _C1_MAXW:
+            return _ALL_ATEN
+        return Conv5Plan("pool1" if pooled and Ho % 2 == 0 else "aten",
+                         "aten", "wrw1")
 
     # pool16 (CI=16) stages 120 pixels; CI=4 has the LDS kernel up to
     # 232 and the register-only k_conv5_pool_nhwc<4> beyond
@@ -237,6 +286,10 @@ def _conv5_indices(weight_shape, device) -> _Conv5Index:
     if ent is None:
         CO, CIr = key[0][:2]
         wrw, t16 = (None, 0)
+        if (CIr, CO) == _C1_SHAPE:
+            ent = _index_cache[key] = _Conv5Index(
+                build_c1_fwd_index(key[0]).to(device), None, None, 0)
+            return ent
         if (((CIr + 3) & ~3), CO) in _WRW_SHAPES:
             wrw, t16 = build_wrw_unpack_index(key[0])
             wrw = wrw.to(device)
@@ -252,12 +305,14 @@ def _conv5_indices(weight_shape, device) -> _Conv5Index:
 
 def _nhwc_bf16(x: torch.Tensor) -> torch.Tensor:
     """Input as NHWC bf16, channels zero-padded to a multiple of 4
-    (conv1: 3 -> 4, one fused kernel)."""
+    (conv1: 3 -> 4, one fused kernel; any other count through F.pad)."""
     N, CIr, Hi, Wi = x.shape
     if CIr % 4 == 0:
         return x.to(torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
-    assert CIr == 3, "channel pad kernel is 3 -> 4 only"
+    if CIr != 3:
+        return F.pad(x.to(torch.bfloat16), (0, 0, 0, 0, 0, -CIr % 4)) \
+            .contiguous(memory_format=torch.channels_last)
     from geomx_amd import _geops
     xc = x.contiguous(memory_format=torch.channels_last)
     xb = torch.empty(N, 4, Hi, Wi, dtype=torch.bfloat16, device=x.device,
@@ -299,7 +354,7 @@ def unpool_fusable(plan: Conv5Plan) -> Conv5Unpool:
     backward while staging gout into LDS). Every other route reads the
     full-resolution gradient relu_maxpool2_bwd scatters."""
     return Conv5Unpool(dgrad=plan.dgrad == "lds_pad4",
-                       wrw=plan.wrw in ("wrw4", "wrw16"))
+                       wrw=plan.wrw in ("wrw4", "wrw16", "wrw1"))
 
 
 def _pooled_backward(fuse: Conv5Unpool, need_x: bool, need_w: bool, gp,
@@ -366,7 +421,9 @@ def _dgrad(route, go, x_real, weight, idx, mask=None, w_frags=None):
 def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None):
     """(grad_w, grad_b) in the weight's dtype; grad_b None without bias.
     With `mask` (custom routes only) `go` is the pooled gradient."""
-    if route == "aten":
+    if route == "wrw1":
+        gw, gb = wrw1_via_kernel(xb, go, mask)   # xb: the caller's tensor
+    elif route == "aten":
         assert mask is None
         _, gw, gb = torch.ops.aten.convolution_backward(
             go, x_real, weight.detach().to(torch.bfloat16),
@@ -405,13 +462,21 @@ class _Conv5Fn(torch.autograd.Function):
         N, CIr, Hi, Wi = x.shape
         CO = weight.shape[0]
         Ho, Wo = Hi - 4, Wi - 4
-        if plan.fwd == "aten" and plan.wrw == "aten":
+        c1 = "pool1" == plan.fwd or "wrw1" == plan.wrw
+        if c1:
+            # the one-channel kernels read the caller's tensor (they round
+            # fp32 while staging); it is what backward saves
+            xb = x if x.dtype in (torch.float32, torch.bfloat16) \
+                else x.to(torch.bfloat16)
+            xb = xb.detach().contiguous()
+        elif plan.fwd == "aten" and plan.wrw == "aten":
             xb = x.to(torch.bfloat16)
         else:
             xb = _nhwc_bf16(x)
         mask = w_dfrags = None
         if plan.fwd == "aten":
-            args = [xb[:, :CIr], weight.detach().to(torch.bfloat16),
+            args = [xb.to(torch.bfloat16) if c1 else xb[:, :CIr],
+                    weight.detach().to(torch.bfloat16),
                     None if bias is None else bias.detach().to(torch.bfloat16)]
             if pooled:
                 with torch.autocast("cuda", enabled=False):
@@ -428,7 +493,12 @@ class _Conv5Fn(torch.autograd.Function):
             else:
                 w_frags, = _pack_frags(weight, idx.fwd)
             b = bias.detach().float() if bias is not None else torch.Tensor()
-            if plan.fwd == "pool":
+            if plan.fwd == "pool1":
+                out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
+                mask = torch.empty(out.numel(), dtype=torch.uint8,
+                                   device=x.device)
+                _geops.conv5c1_pool(xb, w_frags, b, out, mask, N, Hi, Wi, 0)
+            elif plan.fwd == "pool":
                 out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
                 mask = torch.empty(out.numel(), dtype=torch.uint8,
                                    device=x.device)
@@ -456,6 +526,8 @@ class _Conv5Fn(torch.autograd.Function):
         xb, weight, mask = ctx.saved_tensors
         plan, idx = ctx.plan, ctx.idx
         x_real = xb[:, :ctx.CIr]
+        if plan.wrw == "wrw1" and ctx.needs_input_grad[0]:
+            x_real = xb.to(torch.bfloat16)   # the ATen dgrad's operand
         go = grad_out.to(torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
         need_x = ctx.needs_input_grad[0]
@@ -545,7 +617,7 @@ class GeoConv5Pool(GeoConv5):
     def forward(self, x):
         plan, idx = self._route(x)
         y = self._conv(x, plan, idx)
-        if plan.fwd == "pool":
+        if plan.fwd in ("pool", "pool1"):
             return y
         y = F.max_pool2d(F.relu(y), 2, 2)
         return y if plan == _ALL_ATEN else y.to(_out_dtype(x))
