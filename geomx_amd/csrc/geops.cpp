@@ -1,7 +1,8 @@
 // Torch bindings for the geomx_amd gfx950 kernel library: kernels.hip
 // (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
 // (5x5 conv forward / data gradient), wirereduce.hip (fused decode-and-sum
-// of all parties' wire payloads), dgtencode.hip (fused DGT mode-3 encode),
+// of all parties' wire payloads), wiresparse.hip (the same for the Bi-Sparse
+// lists), dgtencode.hip (fused DGT mode-3 encode),
 // convwrw2.hip (5x5 conv weight gradient, tr16 probes) and fc.hip
 // (NHWC-native first dense layer layout kernels: permuting weight casts,
 // transposing flatten).
@@ -66,6 +67,14 @@ void geops_wire_sum_f16(const void* const*, int, float*, long long, bool,
 void geops_wire_sum_dgt(const float* const*, const int* const*,
                         const uint8_t* const*, const float* const*, int,
                         float*, long long, int, int, int, bool, hipStream_t);
+// wiresparse.hip
+int geops_wire_sum_bsc_tile();
+void geops_wire_sum_bsc(const float* const*, const int* const*, int, int,
+                        float*, long long, bool, hipStream_t);
+void geops_wire_sum_bsc_dgt(const float* const*, const int* const*,
+                            const uint8_t* const*, const float* const*,
+                            const int* const*, int, int, int, int, float*,
+                            long long, bool, hipStream_t);
 // dgtencode.hip
 int geops_dgt_encode(const float*, float*, const float*, const int*, float*,
                      uint8_t*, float*, long long, int, int, int, hipStream_t);
@@ -418,6 +427,92 @@ void wire_sum_dgt(std::vector<torch::Tensor> exacts,
                      out.data_ptr<float>(), numel, (int)chunk, (int)nchunks,
                      (int)n_keep, accumulate, cur_stream());
   launch_check("wire_sum_dgt");
+}
+
+// ---------------------------------------------------------------------------
+// Fused Bi-Sparse wire reduce (wiresparse.hip): out = (accumulate ? out : +0)
+// + the scattered lists of all parties, folded in list order. Every list has
+// the same number of slots; each is in ascending index order with its
+// placeholders (index -1) last, which is not checked here.
+// ---------------------------------------------------------------------------
+
+// what both forms share: out, and the lists' common length
+long long check_bsc_lists(const std::vector<torch::Tensor>& idxs,
+                          const torch::Tensor& out, const char* what) {
+  // not check_f32: the kernel has a scalar path for an `out` (a slice view)
+  // off a 16 B boundary
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+              out.scalar_type() == torch::kFloat32, what,
+              ": out must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(!idxs.empty(), what, " needs at least one party");
+  TORCH_CHECK(out.numel() >= 1 && out.numel() <= INT32_MAX, what,
+              " serves 1 <= n < 2^31, got ", out.numel());
+  const long long k = idxs[0].numel();
+  TORCH_CHECK(k < (1 << 30), what, " serves lists of fewer than 2^30 slots");
+  return k;
+}
+
+void wire_sum_bsc(std::vector<torch::Tensor> vals,
+                  std::vector<torch::Tensor> idxs, torch::Tensor out,
+                  bool accumulate) {
+  const long long k = check_bsc_lists(idxs, out, "wire_sum_bsc");
+  const size_t P = idxs.size();
+  TORCH_CHECK(vals.size() == P,
+              "wire_sum_bsc needs as many value lists as index lists");
+  std::vector<const float*> pv;
+  std::vector<const int*> pi;
+  for (size_t p = 0; p < P; ++p) {
+    pv.push_back((const float*)check_payload(vals[p], out, torch::kFloat32, k,
+                                             "vals", p));
+    pi.push_back((const int*)check_payload(idxs[p], out, torch::kInt32, k,
+                                           "idx", p));
+  }
+  geops_wire_sum_bsc(pv.data(), pi.data(), (int)P, (int)k,
+                     out.data_ptr<float>(), out.numel(), accumulate,
+                     cur_stream());
+  launch_check("wire_sum_bsc");
+}
+
+void wire_sum_bsc_dgt(std::vector<torch::Tensor> exacts,
+                      std::vector<torch::Tensor> keep_idxs,
+                      std::vector<torch::Tensor> packeds,
+                      std::vector<torch::Tensor> minmaxs,
+                      std::vector<torch::Tensor> idxs, torch::Tensor out,
+                      int64_t chunk, bool accumulate) {
+  const long long k = check_bsc_lists(idxs, out, "wire_sum_bsc_dgt");
+  const size_t P = idxs.size();
+  TORCH_CHECK(exacts.size() == P && keep_idxs.size() == P &&
+              packeds.size() == P && minmaxs.size() == P,
+              "wire_sum_bsc_dgt needs the five payload lists equally long");
+  TORCH_CHECK(chunk >= 64 && chunk <= 8192 && (chunk & (chunk - 1)) == 0,
+              "wire_sum_bsc_dgt serves a power-of-two chunk in [64, 8192], "
+              "got ", chunk);
+  TORCH_CHECK(k >= 1, "wire_sum_bsc_dgt needs at least one list slot");
+  const long long nchunks = (k + chunk - 1) / chunk;
+  const long long n_keep = keep_idxs[0].numel();
+  TORCH_CHECK(n_keep <= nchunks, "keep_idx names ", n_keep, " of ", nchunks,
+              " chunks");
+  const long long n_lossy = nchunks - n_keep;
+  std::vector<const float*> pe, pm;
+  std::vector<const int*> pk, pi;
+  std::vector<const uint8_t*> pp;
+  for (size_t p = 0; p < P; ++p) {
+    pe.push_back((const float*)check_payload(
+        exacts[p], out, torch::kFloat32, n_keep * chunk, "exact", p));
+    pk.push_back((const int*)check_payload(
+        keep_idxs[p], out, torch::kInt32, n_keep, "keep_idx", p));
+    pp.push_back((const uint8_t*)check_payload(
+        packeds[p], out, torch::kUInt8, n_lossy * (chunk / 2), "packed", p));
+    pm.push_back((const float*)check_payload(
+        minmaxs[p], out, torch::kFloat32, 2 * n_lossy, "minmax", p));
+    pi.push_back((const int*)check_payload(idxs[p], out, torch::kInt32, k,
+                                           "idx", p));
+  }
+  geops_wire_sum_bsc_dgt(pe.data(), pk.data(), pp.data(), pm.data(),
+                         pi.data(), (int)P, (int)k, (int)chunk, (int)n_keep,
+                         out.data_ptr<float>(), out.numel(), accumulate,
+                         cur_stream());
+  launch_check("wire_sum_bsc_dgt");
 }
 
 // ---------------------------------------------------------------------------
@@ -1244,6 +1339,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wire_sum_2bit", &wire_sum_2bit);
   m.def("wire_sum_f16", &wire_sum_f16);
   m.def("wire_sum_dgt", &wire_sum_dgt);
+  m.def("wire_sum_bsc", &wire_sum_bsc);
+  m.def("wire_sum_bsc_dgt", &wire_sum_bsc_dgt);
+  // output elements per tile of k_wire_sum_bsc
+  m.attr("WIRE_BSC_TILE") = geops_wire_sum_bsc_tile();
   m.def("dgt_encode", &dgt_encode);
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);

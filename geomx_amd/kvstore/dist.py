@@ -573,10 +573,11 @@ class KVStoreDist(KVStoreBase):
                               party_sum: torch.Tensor) -> Optional[List[torch.Tensor]]:
         """Leader-tier exchange. Returns the list of per-party
         contributions on ranks that must apply the update (owner in
-        sharded mode / all leaders in replicated), else None. The dense
-        wire formats (2bit, fp16, DGT mode 3) return their fused sum as a
-        one-element list, except where dist_async applies every party's
-        contribution as an update of its own."""
+        sharded mode / all leaders in replicated), else None. The
+        compressed wire formats (Bi-Sparse lists, 2bit, fp16, DGT mode 3)
+        return their fused sum as a one-element list, except where
+        dist_async applies every party's contribution as an update of its
+        own."""
         topo = self.topo
         P = topo.num_parties
         group = topo.leader_group
@@ -605,22 +606,26 @@ class KVStoreDist(KVStoreBase):
                     comm.all_gather(lst, t, group=group)
                 self.wan.charge(cross_party_bytes(
                     "all_gather", dg.wire_bytes() + idx.numel() * 4, P))
-                dense = []
-                for pi in range(P):
-                    v_p = dg.decompress(*(lst[pi] for lst in gathered[:4]))
-                    dense.append(ops.bsc_decompress(
-                        v_p.contiguous(), gathered[4][pi], st.numel))
-                return dense
+                if per_party:
+                    dense = []
+                    for pi in range(P):
+                        v_p = dg.decompress(
+                            *(lst[pi] for lst in gathered[:4]))
+                        dense.append(ops.bsc_decompress(
+                            v_p.contiguous(), gathered[4][pi], st.numel))
+                    return dense
+                return [ops.wire_sum_bsc(list(zip(*gathered)), st.numel,
+                                         chunk_elems=dg.chunk)]
             payload = vals.numel() * 4 + idx.numel() * 4
             vlist = [torch.empty_like(vals) for _ in range(P)]
             ilist = [torch.empty_like(idx) for _ in range(P)]
             comm.all_gather(vlist, vals, group=group)
             comm.all_gather(ilist, idx, group=group)
             self.wan.charge(cross_party_bytes("all_gather", payload, P))
-            dense = []
-            for v_, i_ in zip(vlist, ilist):
-                dense.append(ops.bsc_decompress(v_, i_, st.numel))
-            return dense
+            if per_party:
+                return [ops.bsc_decompress(v_, i_, st.numel)
+                        for v_, i_ in zip(vlist, ilist)]
+            return [ops.wire_sum_bsc(list(zip(vlist, ilist)), st.numel)]
 
         if ctype == "2bit":
             # the reference also compresses the local->global re-push

@@ -365,6 +365,77 @@ def wire_sum_dgt(payloads, numel: int, chunk_elems: int,
     return ref.wire_sum_dgt(payloads, numel, chunk_elems, out, accumulate)
 
 
+# output elements per tile of k_wire_sum_bsc (None without the extension)
+WIRE_BSC_TILE = getattr(_geops, "WIRE_BSC_TILE", None)
+
+_BSC_WIRE_DTYPES = {
+    2: (torch.float32, torch.int32),
+    5: (torch.float32, torch.int32, torch.uint8, torch.float32, torch.int32),
+}
+
+
+def _wire_sum_bsc_served(payloads, n: int, out: Optional[torch.Tensor],
+                         chunk_elems: Optional[int]) -> bool:
+    """What k_wire_sum_bsc serves: 1 <= n < 2^31, every party's payload of
+    the same form, dtypes and lengths, contiguous, lists of fewer than 2^30
+    slots, a contiguous fp32 `out`; for the coded form a power-of-two chunk
+    in [64, 8192] and at least one slot."""
+    form = len(payloads[0])
+    k = payloads[0][-1].numel()
+    if not 1 <= n < 2 ** 31 or k >= 2 ** 30:
+        return False
+    if form == 5 and (k < 1 or chunk_elems is None
+                      or not 64 <= chunk_elems <= 8192
+                      or chunk_elems & (chunk_elems - 1)):
+        return False
+    if out is not None and (out.dtype != torch.float32 or out.numel() != n
+                            or not out.is_contiguous()):
+        return False
+    first = payloads[0]
+    return all(len(pl) == form
+               and all(t.dtype == d and t.is_contiguous()
+                       and t.numel() == f.numel()
+                       for t, d, f in zip(pl, _BSC_WIRE_DTYPES[form], first))
+               for pl in payloads)
+
+
+def wire_sum_bsc(payloads, n: int, out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False,
+                 chunk_elems: Optional[int] = None) -> torch.Tensor:
+    """Dense sum of the Bi-Sparse lists of all parties, in party order. A
+    payload is (vals f32[k], idx i32[k]) or, with `chunk_elems`, the coded
+    form (exact, keep_idx, packed, minmax, idx): the DGTState.compress tuple
+    of the zero-masked values, and the exact indices. Entries with idx < 0
+    (placeholders) or idx >= n are skipped.
+
+    Precondition: every list is in ascending index order with its
+    placeholders last, as every packer writes it (bsc_compress,
+    bsc_pull_compress). For a list that breaks this the values of the result
+    are unspecified (no address leaves the operands). On the GPU one kernel
+    does the whole sum; operands outside what it serves, and CPU tensors,
+    take the op sequence of ref.wire_sum_bsc, whose bits it reproduces."""
+    if not payloads or len(payloads[0]) not in _BSC_WIRE_DTYPES:
+        raise ValueError("wire_sum_bsc needs at least one party, and 2 or 5 "
+                         "tensors per payload")
+    if _on_gpu(out, *(t for p in payloads for t in p)) \
+            and _wire_sum_bsc_served(payloads, n, out, chunk_elems):
+        g = _require_native()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32,
+                              device=payloads[0][0].device)
+            accumulate = False
+        lists = [list(x) for x in zip(*payloads)]
+        if len(lists) == 2:
+            g.wire_sum_bsc(lists[0], lists[1], _flat_inplace(out, "out"),
+                           accumulate)
+        else:
+            lists[3] = [m.reshape(-1) for m in lists[3]]
+            g.wire_sum_bsc_dgt(*lists, _flat_inplace(out, "out"), chunk_elems,
+                               accumulate)
+        return out
+    return ref.wire_sum_bsc(payloads, n, out, accumulate, chunk_elems)
+
+
 # ---------------------------------------------------------------------------
 # Fused optimizer updates
 # ---------------------------------------------------------------------------

@@ -354,6 +354,24 @@ def wire_sum_dgt(payloads, numel: int, chunk_elems: int,
     return acc if out is None else out
 
 
+def wire_sum_bsc(payloads, n: int, out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False,
+                 chunk_elems: Optional[int] = None) -> torch.Tensor:
+    """Dense sum of the Bi-Sparse lists of all parties: `acc = out or
+    zeros`, then per party `acc[idx] += value`. A payload is (vals, idx) or,
+    with `chunk_elems`, (exact, keep_idx, packed, minmax, idx): the values
+    as a DGT mode-3 payload over the list positions. Entries with idx < 0
+    (placeholders) or idx >= n are skipped."""
+    acc = _wire_acc(n, payloads[0][-1].device, out, accumulate)
+    for pl in payloads:
+        idx = pl[-1]
+        vals = pl[0] if len(pl) == 2 else dgt_decompress(
+            *pl[:4], idx.numel(), chunk_elems)
+        inside = idx < n
+        bsc_decompress(vals[inside], idx[inside], n, out=acc, accumulate=True)
+    return acc if out is None else out
+
+
 # ---------------------------------------------------------------------------
 # FP16 transmission helpers (fp32 master copy semantics)
 # ---------------------------------------------------------------------------

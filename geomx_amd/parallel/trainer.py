@@ -466,14 +466,11 @@ class GeoTrainer:
                     self.wan.charge(cross_party_bytes(
                         "all_gather",
                         b.dgt.wire_bytes() + idx.numel() * 4, P))
-                    acc = torch.zeros_like(b.flat)
-                    for p_ in range(P):
-                        v_p = b.dgt.decompress(
-                            *(lst[p_] for lst in gathered[:4]))
-                        ops.bsc_decompress(v_p, gathered[4][p_],
-                                           b.flat.numel(), out=acc,
-                                           accumulate=True)
-                    b.flat.copy_(acc)
+                    # one fused decode-and-scatter-sum of all parties'
+                    # lists; b.flat is no input of the sum: the payload was
+                    # made from it above
+                    ops.wire_sum_bsc(list(zip(*gathered)), b.flat.numel(),
+                                     out=b.flat, chunk_elems=b.dgt.chunk)
                 elif ctype == "bsc" or ctype == "mpq":
                     if b.bsc_u is None:
                         b.bsc_u = torch.zeros_like(b.flat)
@@ -486,11 +483,9 @@ class GeoTrainer:
                     comm.all_gather(ilist, idx, group=topo.leader_group)
                     self.wan.charge(cross_party_bytes(
                         "all_gather", vals.numel() * 8, P))
-                    acc = torch.zeros_like(b.flat)
-                    for v_, i_ in zip(vlist, ilist):
-                        ops.bsc_decompress(v_, i_, b.flat.numel(),
-                                           out=acc, accumulate=True)
-                    b.flat.copy_(acc)
+                    # b.flat is no input of the sum, as above
+                    ops.wire_sum_bsc(list(zip(vlist, ilist)),
+                                     b.flat.numel(), out=b.flat)
                 elif ctype == "dgt":
                     if b.dgt is None:
                         from ..kvstore.dgt import DGTState

@@ -162,13 +162,90 @@ def wire_reduce_rows(n, iters, report, results):
         torch.cuda.empty_cache()
 
 
+def wire_sparse_rows(n, iters, report, results):
+    """Fused Bi-Sparse wire reduce (ops.wire_sum_bsc) against the two chains
+    it replaced, ratio 0.01, P = 2 and 8, plain lists and the bsc_dgt coded
+    form (chunk 1024, k = 0.5): the kvstore chain (P dense decodes, P - 1
+    out-of-place adds) and the trainer chain (zeros, P accumulating unpacks,
+    copy_). Each chain is timed against the fused op in alternating
+    windows of its own. Bytes are those that must move: every party's
+    payload in, 4n out. The spread is (max - min) / median over the 7
+    windows."""
+    from geomx_amd.kvstore.dgt import DGTState
+    dev = "cuda:0"
+    chunk = 1024
+    dst = torch.empty(n, device=dev)
+    iters = max(5, iters // 5)
+
+    def med(ts):
+        return sorted(ts)[len(ts) // 2]
+
+    for P in (2, 8):
+        plain, coded, sts = [], [], []
+        u, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        for p in range(P):
+            g = torch.randn(n, device=dev, generator=torch.Generator(
+                device=dev).manual_seed(40 + p))
+            vals, idx = ops.bsc_compress(g, u.zero_(), v.zero_(), 0.01)
+            plain.append((vals, idx))
+            st = DGTState(vals.numel(), dev, chunk_elems=chunk, k=0.5, mode=3)
+            coded.append(st.compress(vals.masked_fill(idx < 0, 0.0)) + (idx,))
+            sts.append(st)
+        del g, u, v
+
+        for name, pls, ce in (("wire_sum_bsc", plain, None),
+                              ("wire_sum_bsc(dgt k=.5)", coded, chunk)):
+            def values(p):
+                if ce is None:
+                    return pls[p][0]
+                return sts[p].decompress(*pls[p][:4]).contiguous()
+
+            def chain_kvstore():
+                dense = [ops.bsc_decompress(values(p), pls[p][-1], n)
+                         for p in range(P)]
+                agg = dense[0]
+                for c in dense[1:]:
+                    agg = agg + c
+                return agg
+
+            def chain_trainer():
+                acc = torch.zeros(n, device=dev)
+                for p in range(P):
+                    ops.bsc_decompress(values(p), pls[p][-1], n, out=acc,
+                                       accumulate=True)
+                dst.copy_(acc)
+
+            nbytes = 4 * n + sum(t.numel() * t.element_size()
+                                 for pl in pls for t in pl)
+            for site, fused, chain in (
+                    ("kvstore", lambda: ops.wire_sum_bsc(pls, n,
+                                                         chunk_elems=ce),
+                     chain_kvstore),
+                    ("trainer", lambda: ops.wire_sum_bsc(pls, n, out=dst,
+                                                         chunk_elems=ce),
+                     chain_trainer)):
+                tf, tc = window_pair(fused, chain, iters)
+                mf, mc = med(tf), med(tc)
+                report("%s P=%d %s" % (name, P, site), nbytes, mf)
+                results[-1].update(
+                    chain_ms=round(mc * 1e3, 4), speedup=round(mc / mf, 2),
+                    spread=round((max(tf) - min(tf)) / mf, 3),
+                    chain_spread=round((max(tc) - min(tc)) / mc, 3))
+                print("%24s chain %8.3f ms, fused is %.2fx; spread between "
+                      "windows %.1f%% fused, %.1f%% chain"
+                      % ("", mc * 1e3, mc / mf, 100 * results[-1]["spread"],
+                         100 * results[-1]["chain_spread"]))
+        del plain, coded, sts
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 26)  # 64M fp32 = 256 MB
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--json-out", type=str, default=None)
     ap.add_argument("--only-wire", action="store_true",
-                    help="only the wire reduce rows")
+                    help="only the wire reduce rows, dense and sparse")
     ap.add_argument("--only-dgt", action="store_true",
                     help="only the fused DGT encode rows")
     args = ap.parse_args()
@@ -196,7 +273,9 @@ def main():
                           f, indent=1)
 
     if args.only_wire:
+        del g
         wire_reduce_rows(n, args.iters, report, results)
+        wire_sparse_rows(n, args.iters, report, results)
         dump()
         return
     if args.only_dgt:
@@ -310,6 +389,7 @@ def main():
     del w, m, vv, pw, u, v, g, r, out, p4
     torch.cuda.empty_cache()
     wire_reduce_rows(n, args.iters, report, results)
+    wire_sparse_rows(n, args.iters, report, results)
     dgt_encode_rows(n, args.iters, report, results)
     dump()
 

@@ -39,12 +39,14 @@ ext = CUDAExtension(
 # to scalar fp32 VALU ops only. dgtencode.hip is kept to scalar fp32 ops in
 # the same way; there the switch changes no result, only registers (204
 # VGPRs with packed fp32 on against 156 at chunk 8192, docs/kernels.md).
+# wiresparse.hip folds the Bi-Sparse lists in the same stated order.
 # conv1c.hip (the CI = 1 conv stage) sums its four waves' slabs in a
 # stated order and is built the same way.
 # The extension's flag list is one for all of its sources, so these are
 # compiled here, with the same flags plus the feature switch, and linked
 # into _geops as objects. They include no torch header.
 NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
+                     "geomx_amd/csrc/wiresparse.hip",
                      "geomx_amd/csrc/dgtencode.hip",
                      "geomx_amd/csrc/conv1c.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h",
