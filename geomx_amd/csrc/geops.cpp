@@ -2,7 +2,8 @@
 // (kvstore compression, optimizer updates, fused ReLU+pool), conv.hip
 // (5x5 conv forward / data gradient), wirereduce.hip (fused decode-and-sum
 // of all parties' wire payloads), wiresparse.hip (the same for the Bi-Sparse
-// lists), dgtencode.hip (fused DGT mode-3 encode),
+// lists), dgtencode.hip (fused DGT mode-3 encode), bscselect.hip (Bi-Sparse
+// boundary select),
 // convwrw2.hip (5x5 conv weight gradient, tr16 probes) and fc.hip
 // (NHWC-native first dense layer layout kernels: permuting weight casts,
 // transposing flatten).
@@ -78,6 +79,13 @@ void geops_wire_sum_bsc_dgt(const float* const*, const int* const*,
 // dgtencode.hip
 int geops_dgt_encode(const float*, float*, const float*, const int*, float*,
                      uint8_t*, float*, long long, int, int, int, hipStream_t);
+// bscselect.hip
+int geops_bsc_boundary_cap();
+int geops_bsc_boundary_grid(long long, int);
+long long geops_bsc_boundary_ws_words(long long);
+void geops_bsc_boundary(const float*, const float*, const float*, const int*,
+                        long long, long long, long long, float, float*,
+                        uint32_t*, int, hipStream_t);
 // rowsparse.hip
 void geops_rsp_merge(const long long*, const long long*, const long long*,
                      const float*, long long*, float*, long long, long long,
@@ -263,6 +271,67 @@ bool bsc_compress_fused(torch::Tensor g, torch::Tensor u, torch::Tensor v,
       (float)mu, n, vals.numel(), (float)placeholder, cur_stream());
   launch_check("bsc_compress_fused");
   return rc == 0;
+}
+
+// ---------------------------------------------------------------------------
+// Bi-Sparse boundary select (bscselect.hip): out[0] = the k-th largest
+// |v[i] + (u[i]*mu + g[i])| (g and u given) or |v[i]| (both empty) over
+// the sample positions i = si[0..S). n_wg: 0 lets the launcher choose, 1
+// forces the one-workgroup form, >= 2 the ticket form on that many
+// workgroups (the hook of the tests and the grid sweep).
+// ---------------------------------------------------------------------------
+
+void bsc_boundary(torch::Tensor v, torch::Tensor g, torch::Tensor u,
+                  torch::Tensor si, int64_t k, double mu, torch::Tensor out,
+                  int64_t n_wg) {
+  // not check_f32: the gathers are 4 B reads, v may be a view off a 16 B
+  // boundary
+  auto check = [&](const torch::Tensor& t, torch::ScalarType dtype,
+                   const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == v.device(), "bsc_boundary: ",
+                name, " must be a GPU tensor on v's device");
+    TORCH_CHECK(t.is_contiguous(), "bsc_boundary: ", name,
+                " must be contiguous");
+    TORCH_CHECK(t.scalar_type() == dtype, "bsc_boundary: ", name,
+                " must be ", dtype, ", got ", t.scalar_type());
+  };
+  check(v, torch::kFloat32, "v");
+  check(si, torch::kInt32, "si");
+  check(out, torch::kFloat32, "out");
+  // torch.Tensor() from Python is an empty tensor, as for dcasgd's mom
+  const bool mom = g.defined() && g.numel() > 0;
+  TORCH_CHECK(mom == (u.defined() && u.numel() > 0),
+              "bsc_boundary takes g and u together or neither");
+  const long long n = v.numel(), S = si.numel();
+  if (mom) {
+    check(g, torch::kFloat32, "g");
+    check(u, torch::kFloat32, "u");
+    TORCH_CHECK(g.numel() == n && u.numel() == n,
+                "bsc_boundary: g and u must have as many elements as v");
+  }
+  TORCH_CHECK(n >= 1 && n <= INT32_MAX, "bsc_boundary serves 1 <= n < 2^31, "
+              "got ", n);
+  TORCH_CHECK(S <= INT32_MAX, "bsc_boundary serves fewer than 2^31 samples");
+  TORCH_CHECK(k >= 1 && k <= S, "bsc_boundary needs 1 <= k <= S, got k = ", k,
+              ", S = ", S);
+  TORCH_CHECK(out.numel() >= 1, "bsc_boundary: out needs one element");
+  TORCH_CHECK(n_wg >= 0 && n_wg <= 65535, "bsc_boundary: n_wg out of range");
+  const int grid = geops_bsc_boundary_grid(S, (int)n_wg);
+  TORCH_CHECK(grid >= 1, "bsc_boundary: the one-workgroup form holds ",
+              geops_bsc_boundary_cap(), " samples, got ", S);
+  torch::Tensor ws;
+  if (grid > 1)
+    ws = torch::empty({geops_bsc_boundary_ws_words(S)},
+                      torch::TensorOptions().dtype(torch::kInt32)
+                          .device(v.device()));
+  geops_bsc_boundary(v.data_ptr<float>(),
+                     mom ? g.data_ptr<float>() : nullptr,
+                     mom ? u.data_ptr<float>() : nullptr,
+                     si.data_ptr<int32_t>(), S, k, n, (float)mu,
+                     out.data_ptr<float>(),
+                     grid > 1 ? (uint32_t*)ws.data_ptr<int32_t>() : nullptr,
+                     grid, cur_stream());
+  launch_check("bsc_boundary");
 }
 
 void bsc_pull_pack(torch::Tensor x, torch::Tensor vals, torch::Tensor idx,
@@ -1333,6 +1402,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsc_pull_pack", &bsc_pull_pack);
   m.def("bsc_compress_fused", &bsc_compress_fused);
   m.def("bsc_unpack", &bsc_unpack);
+  m.def("bsc_boundary", &bsc_boundary);
+  // samples the one-workgroup form of k_bsc_boundary holds in LDS
+  m.attr("BSC_BOUNDARY_CAP") = geops_bsc_boundary_cap();
   m.def("dgt_contribution", &dgt_contribution);
   m.def("quantize_4bit", &quantize_4bit);
   m.def("dequantize_4bit", &dequantize_4bit);

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "bsc_mom.h"
 #include "optim_rules.h"
 #include "wire_codec.h"
 
@@ -100,16 +101,8 @@ extern "C" __global__ void k_dequantize_2bit(const uint32_t* __restrict__ in,
 // Bi-Sparse: fused momentum correction (u = mu*u + g ; v += u)
 // ---------------------------------------------------------------------------
 
-// u*mu and + g are rounded SEPARATELY (no FMA contraction), exactly as
-// the golden model (two torch ops) and the sampled boundary prediction
-// do: the boundary is the |v| of one sampled element, so a fused
-// multiply-add that lands one ulp below it would drop that element, and
-// a mixed CPU/GPU party would drift apart in u and v.
-__device__ __forceinline__ float bsc_mom(float u, float mu, float g) {
-#pragma clang fp contract(off)
-  const float p = u * mu;
-  return p + g;
-}
+// bsc_mom (u*mu and + g rounded separately) lives in bsc_mom.h, shared with
+// the boundary select of bscselect.hip.
 
 extern "C" __global__ void k_bsc_momentum(const float* __restrict__ g,
                                           float* __restrict__ u,

@@ -109,9 +109,10 @@ def bsc_compress(grad, u, v, ratio, momentum=ref.BSC_MOMENTUM, seed=42
         gflat = grad.reshape(-1)
         u, v = _flat_inplace(u, "u"), _flat_inplace(v, "v")
         # boundary PREDICTED from the seeded sample of post-momentum v
-        # (v + mu*u + g at the sample positions) as a DEVICE scalar, so
-        # the fused kernel path never synchronizes with the host
-        bt = _bsc_boundary_pred_gpu(gflat, u, v, ratio, momentum, seed)
+        # (v + mu*u + g at the sample positions, read BEFORE the fused
+        # kernel mutates them) as a DEVICE scalar, so the fused kernel
+        # path never synchronizes with the host
+        bt = bsc_boundary(v, ratio, seed, g=gflat, u=u, momentum=momentum)
         if g.bsc_compress_fused(gflat, u, v, vals, idx, bt, momentum,
                                 ref.BSC_PLACEHOLDER):
             return vals, idx
@@ -126,54 +127,82 @@ def bsc_compress(grad, u, v, ratio, momentum=ref.BSC_MOMENTUM, seed=42
 _bsc_idx_cache: dict = {}
 
 
-def _bsc_sample_idx(n: int, sample_size: int, seed: int, device):
-    ck = (n, sample_size, seed, device)
+def _bsc_sample_idx(n: int, sample_size: int, seed: int, device,
+                    dtype=torch.int64):
+    """Seeded sample positions on `device`, generated once per (n,
+    sample_size, seed) on the CPU generator. int32 is what k_bsc_boundary
+    reads, int64 what the ATen expression indexes with."""
+    ck = (n, sample_size, seed, device, dtype)
     idx = _bsc_idx_cache.get(ck)
     if idx is None:
         if len(_bsc_idx_cache) > 64:
             _bsc_idx_cache.clear()
-        idx = ref.bsc_sample_indices(n, sample_size, seed).to(device)
+        idx = ref.bsc_sample_indices(n, sample_size, seed).to(
+            device=device, dtype=dtype)
         _bsc_idx_cache[ck] = idx
     return idx
 
 
-def _bsc_boundary_pred_gpu(g: torch.Tensor, u: torch.Tensor,
-                           v: torch.Tensor, ratio: float, momentum: float,
-                           seed: int) -> torch.Tensor:
-    """Sampled top-k boundary over the POST-momentum |v|, computed from
-    (g,u,v) BEFORE the fused kernel mutates them: same value the CPU
-    golden model derives after its momentum pass (same seeded sample,
-    same op order mu*u + g then + v). Returns a device fp32 scalar."""
+# samples the one-workgroup form of k_bsc_boundary holds (None without the
+# extension)
+BSC_BOUNDARY_CAP = getattr(_geops, "BSC_BOUNDARY_CAP", None)
+
+
+def _bsc_boundary_served(n: int, sample_size: int, *operands) -> bool:
+    """What k_bsc_boundary serves: contiguous fp32 GPU operands, n < 2^31
+    and at least one sample. The kernel beats the ATen chain at every
+    sample size measured (docs/kernels.md), so no size range is held back."""
+    return (n < 2 ** 31 and sample_size >= 1
+            and all(t.is_cuda and t.dtype == torch.float32
+                    and t.is_contiguous() for t in operands))
+
+
+def bsc_boundary(v: torch.Tensor, ratio: float, seed: int = 42,
+                 g: Optional[torch.Tensor] = None,
+                 u: Optional[torch.Tensor] = None,
+                 momentum: float = ref.BSC_MOMENTUM) -> torch.Tensor:
+    """Sampled top-k boundary of Bi-Sparse as a one-element fp32 tensor: the
+    k-th largest |v| over the seeded sample of ref.bsc_boundary, or, with
+    `g` and `u`, of the POST-momentum |v + (momentum*u + g)| computed from
+    (g, u, v) as they are before the momentum pass (same op order as the
+    golden model, so the same bits). On the GPU one select kernel writes it
+    into storage of its own (k_bsc_fused reads it with a uniform scalar
+    load) and the host never waits; operands the kernel does not serve, and
+    CPU tensors, take the ATen expression."""
+    if (g is None) != (u is None):
+        raise ValueError("bsc_boundary takes g and u together or neither")
+    mom = g is not None
     n = v.numel()
     sample_size = min(ref.bsc_sample_size(n, ratio), n)
-    top_k = max(1, int(sample_size * ratio))
+    k = min(max(1, int(sample_size * ratio)), sample_size)
+    operands = (v, g, u) if mom else (v,)
+    if _on_gpu(*operands) and _bsc_boundary_served(n, sample_size, *operands):
+        si = _bsc_sample_idx(n, sample_size, seed, v.device, torch.int32)
+        out = torch.empty(1, dtype=torch.float32, device=v.device)
+        # contiguous: these are views. Empty tensors for the |v| form
+        gu = (g.reshape(-1), u.reshape(-1)) if mom \
+            else (torch.Tensor(), torch.Tensor())
+        _require_native().bsc_boundary(v.reshape(-1), *gu, si, k, momentum,
+                                       out, 0)
+        return out
     si = _bsc_sample_idx(n, sample_size, seed, v.device)
-    sample = (v[si] + (u[si] * momentum + g[si])).abs()
-    k = min(top_k, sample.numel())
-    # clone: a slice view is 4B-aligned at best; the kernel's
+    flat = v.reshape(-1)
+    if mom:
+        sample = (flat[si] + (u.reshape(-1)[si] * momentum
+                              + g.reshape(-1)[si])).abs()
+    else:
+        sample = flat[si].abs()
+    # clone: a slice view is 4B-aligned at best; the fused kernel's
     # uniform scalar load wants its own 16B-aligned storage
     return torch.topk(sample, k).values[k - 1:k].clone()
 
 
 def _bsc_boundary_gpu(v: torch.Tensor, ratio: float, seed: int) -> float:
-    """Same seeded-sample estimator as the CPU golden model
-    (ref.bsc_boundary): gather |v| at precomputed random positions,
-    small topk. Indices are generated once per (n, sample_size, seed)
-    on the CPU generator and cached on-device, so the per-call cost is
-    one tiny gather + topk."""
-    n = v.numel()
-    sample_size = min(ref.bsc_sample_size(n, ratio), n)
-    top_k = max(1, int(sample_size * ratio))
-    ck = (n, sample_size, seed, v.device)
-    idx = _bsc_idx_cache.get(ck)
-    if idx is None:
-        if len(_bsc_idx_cache) > 64:
-            _bsc_idx_cache.clear()
-        idx = ref.bsc_sample_indices(n, sample_size, seed).to(v.device)
-        _bsc_idx_cache[ck] = idx
-    sample = v[idx].abs()
-    k = min(top_k, sample.numel())
-    return torch.topk(sample, k).values[-1].item()
+    """Boundary of the huge-n fallback route as a host float: the same
+    seeded-sample estimator as the CPU golden model (ref.bsc_boundary) over
+    the post-momentum |v|. That route synchronizes anyway, for bsc_pack's
+    float argument."""
+    return bsc_boundary(v, ratio, seed).item()
 
 
 def bsc_pull_compress(x: torch.Tensor, capacity: int

@@ -63,6 +63,43 @@ def median_pair(fn_a, fn_b, iters, reps=7):
     return sorted(ta)[reps // 2], sorted(tb)[reps // 2]
 
 
+def bsc_boundary_rows(n, iters, report, results, small_n=200_000):
+    """Sampled Bi-Sparse boundary, ratio 0.01, at n and at one small bucket:
+    the ATen chain ops.bsc_boundary replaced (gathers, multiply, adds, abs,
+    topk, slice, clone; kept here as the yardstick) against the op, in 5
+    alternating windows. Bytes are the 16 S of the three 4 B gathers and the
+    positions. The spread is (max - min) / median over the windows."""
+    import geomx_amd.ops as _ops
+    from geomx_amd.ops import reference as ref
+    dev = "cuda:0"
+    ratio, mu = 0.01, ref.BSC_MOMENTUM
+
+    def chain(g, u, v):
+        nn = v.numel()
+        sample_size = min(ref.bsc_sample_size(nn, ratio), nn)
+        top_k = max(1, int(sample_size * ratio))
+        si = _ops._bsc_sample_idx(nn, sample_size, 42, v.device)
+        sample = (v[si] + (u[si] * mu + g[si])).abs()
+        k = min(top_k, sample.numel())
+        return torch.topk(sample, k).values[k - 1:k].clone()
+
+    for nn in (n, small_n):
+        g, u, v = (torch.randn(nn, device=dev) for _ in range(3))
+        assert torch.equal(chain(g, u, v),
+                           _ops.bsc_boundary(v, ratio, g=g, u=u, momentum=mu))
+        ta, tb = window_pair(
+            lambda: chain(g, u, v),
+            lambda: _ops.bsc_boundary(v, ratio, g=g, u=u, momentum=mu),
+            iters, reps=5)
+        S = min(ref.bsc_sample_size(nn, ratio), nn)
+        for name, t in (("bsc_boundary chain", ta), ("bsc_boundary", tb)):
+            t = sorted(t)
+            report("%s n=%d" % (name, nn), 16 * S, t[2])
+            results[-1]["spread"] = round((t[-1] - t[0]) / t[2], 3)
+            print("    spread %.1f %%" % (100 * results[-1]["spread"]))
+        del g, u, v
+
+
 def dgt_encode_rows(n, iters, report, results):
     """Fused DGT mode-3 encode against the op chain it replaced in
     DGTState.compress (ref.dgt_encode on the GPU), chunk 1024, k = 0.5 and
@@ -246,6 +283,8 @@ def main():
     ap.add_argument("--json-out", type=str, default=None)
     ap.add_argument("--only-wire", action="store_true",
                     help="only the wire reduce rows, dense and sparse")
+    ap.add_argument("--only-bsc-boundary", action="store_true",
+                    help="only the Bi-Sparse boundary rows, chain and kernel")
     ap.add_argument("--only-dgt", action="store_true",
                     help="only the fused DGT encode rows")
     args = ap.parse_args()
@@ -276,6 +315,11 @@ def main():
         del g
         wire_reduce_rows(n, args.iters, report, results)
         wire_sparse_rows(n, args.iters, report, results)
+        dump()
+        return
+    if args.only_bsc_boundary:
+        del g
+        bsc_boundary_rows(n, args.iters, report, results)
         dump()
         return
     if args.only_dgt:
@@ -324,6 +368,8 @@ def main():
     import geomx_amd.ops as _ops
     sec = timeit(lambda: _ops.bsc_compress(g, u, v, 0.01), args.iters)
     report("bsc_compress e2e", n * 4 * 5, sec)
+
+    bsc_boundary_rows(n, args.iters, report, results)
 
     sec = timeit(lambda: geops.bsc_pull_pack(out, vals, idx, -65530.0),
                  args.iters)

@@ -41,15 +41,18 @@ ext = CUDAExtension(
 # VGPRs with packed fp32 on against 156 at chunk 8192, docs/kernels.md).
 # wiresparse.hip folds the Bi-Sparse lists in the same stated order.
 # conv1c.hip (the CI = 1 conv stage) sums its four waves' slabs in a
-# stated order and is built the same way.
+# stated order and is built the same way. bscselect.hip forms its keys with
+# one rounded multiply and two rounded additions (bsc_mom.h) and is too.
 # The extension's flag list is one for all of its sources, so these are
 # compiled here, with the same flags plus the feature switch, and linked
 # into _geops as objects. They include no torch header.
 NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
                      "geomx_amd/csrc/wiresparse.hip",
                      "geomx_amd/csrc/dgtencode.hip",
-                     "geomx_amd/csrc/conv1c.hip"]
+                     "geomx_amd/csrc/conv1c.hip",
+                     "geomx_amd/csrc/bscselect.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h",
+                     "geomx_amd/csrc/bsc_mom.h",
                      "geomx_amd/csrc/conv5_common.h"]
 NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 ext.depends += NO_PK_F32_SOURCES + NO_PK_F32_DEPENDS
