@@ -33,8 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "conv5_common.h"
-
-#define CONV_THREADS 256  // 4 waves
+#include "conv5_pool2.h"  // k_conv5_pool2_nhwc, CONV_THREADS
 
 template <int CI, int COT>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_nhwc(
@@ -313,177 +312,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool_nhwc(
 // bit-identical to theirs.
 // ---------------------------------------------------------------------
 
-// conv1 stage. A tile's chunk km reads, per conv row, 16 B at pixel wo
-// of staged row r + kh (two ds_read_b64: odd wo is only 8 B aligned);
-// slots past S hit the next pixel's data, zeroed by the Sp padding in
-// w_frags. The walk is flattened over (tile, km): the reads of the next
-// step are issued before the 4 MFMAs (one per conv row) of this one,
-// across tiles too. A lane pools to 2 pixels x 2 pooled rows of channel
-// m; quad_tr4 turns them into 4 channels of one (pooled row, pixel):
-// one 8-byte out store and one 4-byte mask store per lane and tile.
-template <int PIX>
-__global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
-    const bf16_t* __restrict__ in,       // [N][Hi][Wi][4]
-    const bf16_t* __restrict__ w_frags,  // [1][nK][64][8]
-    const float* __restrict__ bias,      // [16] or nullptr
-    bf16_t* __restrict__ out,            // [N][Hop][Wop][16]
-    uint8_t* __restrict__ mask,          // [N*Hop*Wop*16]
-    int Nn, int Hi, int Wi, int Ho, int Wo) {
-  constexpr int CI = 4;
-  constexpr int S = 5 * CI;             // 20
-  constexpr int Sp = (S + 7) & ~7;      // 24
-  constexpr int K = 5 * Sp;             // 120
-  constexpr int nK = (K + 31) / 32;     // 4
-  constexpr int CO = 16;
-  using Rows = RowImage<PIX, CI, true>;   // bank skew per row
-  constexpr int NCHA = Rows::NCH;
-  constexpr int ARPB = Rows::PITCH;
-  constexpr int ROWS = 4;                 // conv rows per block
-  constexpr int NROW = ROWS + 4;
-  constexpr int IMG = NROW * ARPB;
-  constexpr int MAXU = Rows::MAXU;        // tiles per wave
-  constexpr int NS = MAXU * nK;           // steps of the walk
-  __shared__ __attribute__((aligned(128))) char lds_rows[2 * IMG];
-
-  const int lane = threadIdx.x & 63;
-  const int p = lane & 15;
-  const int q = lane >> 4;
-  const int m = lane & 15;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-  bf16x8 breg[nK];
-#pragma unroll
-  for (int i = 0; i < nK; ++i)
-    breg[i] = *reinterpret_cast<const bf16x8*>(w_frags + (i * 64 + lane) * 8);
-  const float bias_v = bias ? bias[m] : 0.0f;
-
-  const int Hop = Ho >> 1, Wop = Wo >> 1;
-  const int tiles_w = (Wo + 15) >> 4;
-  const int hblocks = (Hop + 1) >> 1;
-  const long long n_blocks = (long long)Nn * hblocks;
-  const int wg = blockIdx.x;
-  const int n_wg = gridDim.x;
-  const unsigned lds0 = lds_addr(lds_rows);
-
-  // per-lane read address of (tile u, chunk km) in image 0, conv row 0.
-  // A tile past the row clamps to the last pixel: in-bounds, never
-  // stored. The one k-run past K (km 3, q 3) must be ZERO: those lanes
-  // read the last 16 bytes of the row's staged kilobytes instead, which
-  // lie past pixel PIX and are zero-filled in every staged row (a select
-  // after the read cost 16 VALU per tile, 0.007 ms at the flagship).
-  static_assert((nK - 1) * 32 + 2 * 8 < K && (nK - 1) * 32 + 3 * 8 >= K, "");
-  static_assert(Rows::ROW_BYTES + 16 <= NCHA * 1024, "zero tail behind row");
-  unsigned aofs[MAXU][nK];
-#pragma unroll
-  for (int u = 0; u < MAXU; ++u) {
-    const int wo_raw = ((wid + 4 * u) << 4) + p;
-    const int wo = wo_raw < Wo ? wo_raw : (Wo - 1);
-#pragma unroll
-    for (int km = 0; km < nK; ++km) {
-      const int k0 = km * 32 + q * 8;
-      aofs[u][km] = lds0 + (k0 < K ? (unsigned)(wo * (CI * 2) +
-                                                (k0 / Sp) * ARPB +
-                                                (k0 % Sp) * 2)
-                                   : (unsigned)(NCHA * 1024 - 16));
-    }
-  }
-
-  auto stage = [&](long long b, int img) {
-    const long long n = b / hblocks;
-    const int ho0 = (int)(b - n * hblocks) * ROWS;
-    const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
-    stage_rows<CI, NCHA, ARPB, true>(in, n, Hi, Wi, ho0, (nrows + 4) * NCHA,
-                                     wid, lane, lds0, img * IMG);
-  };
-
-  // packed results of one block: lane j = m & 3 holds channels
-  // (m & ~3)..+3 of pooled row j >> 1, pooled pixel 2q + (j & 1) of tile u
-  uint2 pko[MAXU];
-  unsigned pkm[MAXU];
-  auto flush = [&](long long n, int hb, int npr) {
-    const int pr = (m & 3) >> 1;
-    if (pr >= npr) return;
-#pragma unroll
-    for (int u = 0; u < MAXU; ++u) {
-      const int wp = ((wid + 4 * u) << 3) + q * 2 + (m & 1);
-      if (wp < Wop) {
-        const long long off =
-            ((n * Hop + (hb * 2 + pr)) * (long long)Wop + wp) * CO + (m & ~3);
-        *reinterpret_cast<uint2*>(out + off) = pko[u];
-        *reinterpret_cast<unsigned*>(mask + off) = pkm[u];
-      }
-    }
-  };
-
-  long long blk = wg;
-  int img = 0;
-  if (blk < n_blocks) stage(blk, 0);
-  long long pn = 0;
-  int phb = 0, pnpr = 0;
-  for (; blk < n_blocks; blk += n_wg, img ^= 1) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (blk + n_wg < n_blocks) stage(blk + n_wg, img ^ 1);
-    flush(pn, phb, pnpr);
-
-    const long long n = blk / hblocks;
-    const int hb = (int)(blk - n * hblocks);
-    const unsigned ib = (unsigned)(img * IMG);
-    auto ldk = [&](bf16x8(&d)[ROWS], int u, int km) {
-      const unsigned a = aofs[u][km] + ib;
-      typedef __attribute__((ext_vector_type(2))) unsigned uu2;
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        union { struct { uu2 lo, hi; } p; bf16x8 h; } c;
-        c.p.lo = *(const __attribute__((address_space(3)))
-                   uu2*)(uintptr_t)(a + r * ARPB);
-        c.p.hi = *(const __attribute__((address_space(3)))
-                   uu2*)(uintptr_t)(a + r * ARPB + 8);
-        d[r] = c.h;
-      }
-    };
-    bf16x8 f[2][ROWS];
-    ldk(f[0], 0, 0);
-#pragma unroll
-    for (int u = 0; u < MAXU; ++u) {
-      if (wid + 4 * u >= tiles_w) break;
-      f32x4 acc[ROWS];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) acc[r] = (f32x4)0.0f;
-#pragma unroll
-      for (int km = 0; km < nK; ++km) {
-        const int s = u * nK + km;
-        if (s + 1 < NS) ldk(f[(s + 1) & 1], (s + 1) / nK, (s + 1) % nK);
-        // (fenced: left alone, the scheduler sinks the reads to their
-        // MFMAs; 0.003-0.005 ms at the flagship)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-          acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              f[s & 1][r], breg[km], acc[r], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // conv pixel = tile*16 + q*4 + i: horizontal pairs are (i, i+1) of
-      // one lane, vertical pairs two accumulators
-      unsigned ov[2][2], cd[2][2];
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr)
-#pragma unroll
-        for (int pi = 0; pi < 2; ++pi)
-          pool_relu4(acc[2 * pr][2 * pi] + bias_v,
-                     acc[2 * pr][2 * pi + 1] + bias_v,
-                     acc[2 * pr + 1][2 * pi] + bias_v,
-                     acc[2 * pr + 1][2 * pi + 1] + bias_v, ov[pr][pi],
-                     cd[pr][pi]);
-      pko[u] = quad_tr4(ov[0][0], ov[0][1], ov[1][0], ov[1][1], m);
-      pkm[u] = pack_codes(quad_tr4(cd[0][0], cd[0][1], cd[1][0], cd[1][1], m));
-    }
-    pn = n;
-    phb = hb;
-    pnpr = (Ho - hb * ROWS) < ROWS ? 1 : 2;
-  }
-  flush(pn, phb, pnpr);
-}
+// conv1 stage: k_conv5_pool2_nhwc, in conv5_pool2.h.
 
 
 // conv2 stage (CO = COT*16). With CI = 16 a tap row is 80 K-slots = 2.5
@@ -1133,7 +962,8 @@ static int conv5_pool_launch(const bf16_t* in, const bf16_t* w_frags,
   }
   if (CI == 4 && !(Wi & 1) && need <= 232) {
     hipLaunchKernelGGL((k_conv5_pool2_nhwc<232>), grid_of(2048), block, 0, s,
-                       in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo);
+                       in, w_frags, bias, out, mask, Nn, Hi, Wi, Ho, Wo,
+                       (bf16_t*)nullptr);
     return 0;
   }
   if (CI == 4) {

@@ -118,6 +118,10 @@ int geops_conv5_pool_nhwc(const unsigned short*, const unsigned short*,
 int geops_conv5_pool_nwg_nhwc(const unsigned short*, const unsigned short*,
                               const float*, unsigned short*, uint8_t*, int,
                               int, int, int, int, int, int, int, hipStream_t);
+int geops_conv5_pool_x32_nhwc(const float*, const unsigned short*,
+                              const float*, unsigned short*, uint8_t*,
+                              unsigned short*, int, int, int, int, int, int,
+                              int, hipStream_t);
 void geops_pad_ch3to4_nhwc(const void*, unsigned short*, long long, int,
                            hipStream_t);
 int geops_conv5_pack_frags(const float*, long long, const long long*,
@@ -740,6 +744,80 @@ void conv5_pool_nwg_nhwc(torch::Tensor in, torch::Tensor w_frags,
   TORCH_CHECK(rc == 0, "conv5_pool_nwg_nhwc: unsupported geometry CI=", CI,
               " CO=", CO);
   launch_check("conv5_pool_nwg_nhwc");
+}
+
+// conv1 stage from the caller's fp32 image: x is [N][3][Hi][Wi] in
+// channels_last memory (or [N][Hi][Wi][3] contiguous); out and mask as
+// conv5_pool_nhwc gives them for pad_ch3to4_nhwc(x), which is written
+// to xb_out unless that is an empty tensor. The kernel addresses every
+// operand from the geometry alone, so all sizes are checked here.
+// n_wg == 0 is the default grid.
+static void conv5_pool_x32_checked(const char* what, torch::Tensor x,
+                                   torch::Tensor w_frags, torch::Tensor bias,
+                                   torch::Tensor out, torch::Tensor mask,
+                                   torch::Tensor xb_out, int64_t N,
+                                   int64_t Hi, int64_t Wi, int64_t Ho,
+                                   int64_t Wo, int64_t CO, int64_t n_wg) {
+  TORCH_CHECK(x.is_cuda() && w_frags.is_cuda() && out.is_cuda() &&
+              mask.is_cuda(), what, ": operands must be GPU tensors");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 &&
+              w_frags.scalar_type() == torch::kBFloat16 &&
+              out.scalar_type() == torch::kBFloat16 &&
+              mask.scalar_type() == torch::kUInt8, what, ": operand dtype");
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX && Ho >= 2 && Wo >= 2 &&
+              Hi == Ho + 4 && Wi == Wo + 4 && Hi <= INT32_MAX && CO == 16 &&
+              n_wg >= 0 && n_wg <= 65536, what, ": bad size or n_wg");
+  const bool nhwc =
+      x.dim() == 4 &&
+      ((x.size(0) == N && x.size(1) == 3 && x.size(2) == Hi &&
+        x.size(3) == Wi &&
+        x.is_contiguous(at::MemoryFormat::ChannelsLast)) ||
+       (x.size(0) == N && x.size(1) == Hi && x.size(2) == Wi &&
+        x.size(3) == 3 && x.is_contiguous()));
+  TORCH_CHECK(nhwc, what, ": x must hold [N][Hi][Wi][3] densely");
+  TORCH_CHECK(out.numel() == N * (Ho / 2) * (Wo / 2) * CO &&
+              mask.numel() == out.numel() && w_frags.numel() == 4 * 64 * 8,
+              what, ": tensor size mismatch");
+  const bool has_bias = bias.numel() > 0;
+  if (has_bias)
+    TORCH_CHECK(bias.scalar_type() == torch::kFloat32 && bias.is_cuda() &&
+                bias.numel() == CO, what, ": bias must be 16 fp32 on the GPU");
+  const bool has_xb = xb_out.numel() > 0;
+  if (has_xb)
+    TORCH_CHECK(xb_out.is_cuda() &&
+                xb_out.scalar_type() == torch::kBFloat16 &&
+                xb_out.is_non_overlapping_and_dense() &&
+                xb_out.numel() == N * Hi * Wi * 4, what,
+                ": xb_out must hold [N][Hi][Wi][4] bf16");
+  const int rc = geops_conv5_pool_x32_nhwc(
+      x.data_ptr<float>(), (const unsigned short*)w_frags.data_ptr(),
+      has_bias ? bias.data_ptr<float>() : nullptr,
+      (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(),
+      has_xb ? (unsigned short*)xb_out.data_ptr() : nullptr, (int)N, (int)Hi,
+      (int)Wi, (int)Ho, (int)Wo, (int)CO, (int)n_wg, cur_stream());
+  TORCH_CHECK(rc == 0, what, ": unsupported geometry or alignment Hi=", Hi,
+              " Wi=", Wi);
+  launch_check(what);
+}
+
+void conv5_pool_x32_nhwc(torch::Tensor x, torch::Tensor w_frags,
+                         torch::Tensor bias, torch::Tensor out,
+                         torch::Tensor mask, torch::Tensor xb_out, int64_t N,
+                         int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
+                         int64_t CO) {
+  conv5_pool_x32_checked("conv5_pool_x32_nhwc", x, w_frags, bias, out, mask,
+                         xb_out, N, Hi, Wi, Ho, Wo, CO, 0);
+}
+
+// Test hook: conv5_pool_x32_nhwc on a grid of n_wg workgroups.
+void conv5_pool_x32_nwg_nhwc(torch::Tensor x, torch::Tensor w_frags,
+                             torch::Tensor bias, torch::Tensor out,
+                             torch::Tensor mask, torch::Tensor xb_out,
+                             int64_t N, int64_t Hi, int64_t Wi, int64_t Ho,
+                             int64_t Wo, int64_t CO, int64_t n_wg) {
+  TORCH_CHECK(n_wg >= 1, "conv5_pool_x32_nwg_nhwc: n_wg must be positive");
+  conv5_pool_x32_checked("conv5_pool_x32_nwg_nhwc", x, w_frags, bias, out,
+                         mask, xb_out, N, Hi, Wi, Ho, Wo, CO, n_wg);
 }
 
 void conv5_wrw_nhwc(torch::Tensor in, torch::Tensor gout, torch::Tensor part,
@@ -1430,6 +1508,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5c1_wrw", &conv5c1_wrw);
   m.def("conv5c1_wrw_unpool", &conv5c1_wrw_unpool);
   m.def("conv5_pool_nwg_nhwc", &conv5_pool_nwg_nhwc);
+  m.def("conv5_pool_x32_nhwc", &conv5_pool_x32_nhwc);
+  m.def("conv5_pool_x32_nwg_nhwc", &conv5_pool_x32_nwg_nhwc);
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
   m.def("fc_flatten_nchw", &fc_flatten_nchw);

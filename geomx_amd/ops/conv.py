@@ -305,7 +305,10 @@ def _conv5_indices(weight_shape, device) -> _Conv5Index:
 
 def _nhwc_bf16(x: torch.Tensor) -> torch.Tensor:
     """Input as NHWC bf16, channels zero-padded to a multiple of 4
-    (conv1: 3 -> 4, one fused kernel; any other count through F.pad)."""
+    (conv1: 3 -> 4 in one pad kernel; any other count through F.pad).
+    The flagship conv1 stage does not come here: on the 'pool' route an
+    fp32 3-channel image goes to the forward kernel as it is
+    (_x32_operand), and that kernel writes this tensor's bits itself."""
     N, CIr, Hi, Wi = x.shape
     if CIr % 4 == 0:
         return x.to(torch.bfloat16) \
@@ -319,6 +322,22 @@ def _nhwc_bf16(x: torch.Tensor) -> torch.Tensor:
                      memory_format=torch.channels_last)
     _geops.pad_ch3to4_nhwc(xc, xb, N * Hi * Wi)
     return xb
+
+
+def _x32_operand(x: torch.Tensor, plan: Conv5Plan):
+    """The caller's image as conv5_pool_x32_nhwc reads it, or None where
+    that kernel does not serve it, from facts about the tensor alone:
+    fwd 'pool' on a CUDA fp32 3-channel image whose rows are whole 16 B
+    granules (12 * Wi bytes: Wi % 4 == 0, 16 B aligned base), dense in
+    channels_last, and fit the 232-pixel row image of the LDS kernel
+    (wider rows run the register-only forward, which has no fp32 form).
+    Everything else takes _nhwc_bf16 and the pad kernel."""
+    if not (plan.fwd == "pool" and x.is_cuda and x.dtype == torch.float32
+            and x.shape[1] == 3 and x.shape[3] % 4 == 0
+            and _ceil(x.shape[3] - 4, 16) + 4 <= 232):
+        return None
+    xc = x.detach().contiguous(memory_format=torch.channels_last)
+    return xc if xc.data_ptr() % 16 == 0 else None
 
 
 def _w_frags(weight: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -458,12 +477,22 @@ class _Conv5Fn(torch.autograd.Function):
     rounding to bf16 (ties there would route gradient elsewhere)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, plan, idx, pooled):
+    def forward(ctx, x, weight, bias, plan, idx, pooled, x32_input=True):
         N, CIr, Hi, Wi = x.shape
         CO = weight.shape[0]
         Ho, Wo = Hi - 4, Wi - 4
         c1 = "pool1" == plan.fwd or "wrw1" == plan.wrw
-        if c1:
+        x32 = _x32_operand(x, plan) if x32_input else None
+        if x32 is not None:
+            # the forward kernel reads the fp32 image and writes xb, the
+            # bits of _nhwc_bf16(x), for the weight gradient (the only
+            # backward op that reads the input's values; without one no
+            # copy is written and backward keeps the shape alone)
+            xb = None
+            if ctx.needs_input_grad[1] or (bias is not None and
+                                           ctx.needs_input_grad[2]):
+                xb = _empty_nhwc(N, 4, Hi, Wi, x.device)
+        elif c1:
             # the one-channel kernels read the caller's tensor (they round
             # fp32 while staging); it is what backward saves
             xb = x if x.dtype in (torch.float32, torch.bfloat16) \
@@ -502,14 +531,21 @@ class _Conv5Fn(torch.autograd.Function):
                 out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
                 mask = torch.empty(out.numel(), dtype=torch.uint8,
                                    device=x.device)
-                _geops.conv5_pool_nhwc(xb, w_frags, b, out, mask, N, Hi, Wi,
-                                       Ho, Wo, xb.shape[1], CO)
+                if x32 is not None:
+                    _geops.conv5_pool_x32_nhwc(
+                        x32, w_frags, b, out, mask,
+                        torch.Tensor() if xb is None else xb, N, Hi, Wi, Ho,
+                        Wo, CO)
+                else:
+                    _geops.conv5_pool_nhwc(xb, w_frags, b, out, mask, N, Hi,
+                                           Wi, Ho, Wo, xb.shape[1], CO)
             else:
                 out = _empty_nhwc(N, CO, Ho, Wo, x.device)
                 _geops.conv5_nhwc(xb, w_frags, b, out, N, Hi, Wi, Ho, Wo,
                                   xb.shape[1], CO, 0)
         # xb keeps its padded channels: the custom wrw wants CI % 4 == 0,
-        # the ATen routes take the view xb[:, :CIr]
+        # the ATen routes take the view xb[:, :CIr]. On the fp32-image
+        # route xb is the forward kernel's side output (or None).
         # the weight is saved too, so autograd's version check covers the
         # dgrad fragments against an in-place change before backward
         ctx.save_for_backward(xb, weight, mask)
@@ -517,6 +553,7 @@ class _Conv5Fn(torch.autograd.Function):
         ctx.plan, ctx.idx = plan, idx
         ctx.has_bias = bias is not None
         ctx.CIr = CIr
+        ctx.x_shape = tuple(x.shape)
         if out.dtype == torch.float32:  # the module rounds after pooling
             return out
         return out.to(_out_dtype(x))
@@ -525,7 +562,11 @@ class _Conv5Fn(torch.autograd.Function):
     def backward(ctx, grad_out):
         xb, weight, mask = ctx.saved_tensors
         plan, idx = ctx.plan, ctx.idx
-        x_real = xb[:, :ctx.CIr]
+        if xb is None:   # no weight gradient: the dgrad wants the shape
+            x_real = torch.empty(ctx.x_shape, dtype=torch.bfloat16,
+                                 device="meta")
+        else:
+            x_real = xb[:, :ctx.CIr]
         if plan.wrw == "wrw1" and ctx.needs_input_grad[0]:
             x_real = xb.to(torch.bfloat16)   # the ATen dgrad's operand
         go = grad_out.to(torch.bfloat16) \
@@ -548,7 +589,7 @@ class _Conv5Fn(torch.autograd.Function):
             # on another route gets the scattered full-resolution tensor
             def scatter():
                 from geomx_amd import _geops
-                N, _, Hi, Wi = xb.shape
+                N, _, Hi, Wi = ctx.x_shape
                 CO = weight.shape[0]
                 full = _empty_nhwc(N, CO, Hi - 4, Wi - 4, go.device)
                 _geops.relu_maxpool2_bwd(go, mask, full, N, CO, Hi - 4,
@@ -562,7 +603,7 @@ class _Conv5Fn(torch.autograd.Function):
             grad_x = dgrad(go, None) if need_x else None
             grad_wb = wrw(go, None) if need_w else None
         grad_w, grad_b = grad_wb if grad_wb is not None else (None, None)
-        return grad_x, grad_w, grad_b, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None
 
 
 class GeoConv5(torch.nn.Conv2d):
@@ -578,6 +619,9 @@ class GeoConv5(torch.nn.Conv2d):
         super().__init__(in_channels, out_channels, kernel_size=5, **kw)
         self.enabled_shapes = (DEFAULT_ENABLED if enabled_shapes is None
                                else enabled_shapes)
+        # False keeps an fp32 3-channel image on the pad kernel in front
+        # of the forward (the route every other input takes)
+        self.x32_input = True
         self._routes = {}  # (input shape, device) -> (plan, indices)
 
     def _route(self, x):
@@ -599,7 +643,7 @@ class GeoConv5(torch.nn.Conv2d):
         if plan == _ALL_ATEN:
             return torch.nn.Conv2d.forward(self, x)
         return _Conv5Fn.apply(x, self.weight, self.bias, plan, idx,
-                              self._POOLED)
+                              self._POOLED, self.x32_input)
 
     def forward(self, x):
         return self._conv(x, *self._route(x))

@@ -9,7 +9,12 @@ the conv5_pool_nwg_nhwc hook, the grids given with --n-wg.
 Times are per call, device-event-timed over ITERS calls after warm-up;
 each line shows the minimum and the median of --reps such measurements.
 A build without the hook (an older commit) prints its default-grid lines
-only, so the same script times both sides of an A/B."""
+only, so the same script times both sides of an A/B.
+
+Where the build has conv5_pool_x32_nhwc, the conv1 input path is timed
+both ways in the same run (the machines of the pool differ by ~5 %): the
+3 -> 4 channel pad kernel plus the bf16 forward, against the forward that
+reads the fp32 image itself, with and without its padded side output."""
 import argparse
 import os
 import statistics
@@ -44,6 +49,58 @@ def bench(f, reps):
     return min(ts), statistics.median(ts)
 
 
+def x32_ab(reps):
+    torch.manual_seed(5)
+    h, hop = 224, 110
+    x = torch.randn(N, 3, h, h, device=DEV) \
+        .to(memory_format=torch.channels_last)
+    w = torch.randn(16, 3, 5, 5, device=DEV) * 0.05
+    b = torch.randn(16, device=DEV) * 0.1
+    w_frags = C._w_frags(w, C.build_fwd_index(w.shape).to(DEV))
+    outs = [torch.empty(N, hop, hop, 16, device=DEV, dtype=torch.bfloat16)
+            for _ in range(2)]
+    masks = [torch.empty(outs[0].numel(), device=DEV, dtype=torch.uint8)
+             for _ in range(2)]
+    xbs = [C._empty_nhwc(N, 4, h, h, DEV) for _ in range(2)]
+    dims = (N, h, h, h - 4, h - 4)
+
+    def pad():
+        _geops.pad_ch3to4_nhwc(x, xbs[0], N * h * h)
+
+    def fwd():
+        _geops.conv5_pool_nhwc(xbs[0], w_frags, b, outs[0], masks[0], *dims,
+                               4, 16)
+
+    def parent():
+        pad()
+        fwd()
+
+    def fused():
+        _geops.conv5_pool_x32_nhwc(x, w_frags, b, outs[1], masks[1], xbs[1],
+                                   *dims, 16)
+
+    def fused_no_copy():
+        _geops.conv5_pool_x32_nhwc(x, w_frags, b, outs[1], masks[1],
+                                   torch.Tensor(), *dims, 16)
+
+    parent()
+    fused()
+    same = all(torch.equal(a.view(torch.int16), c.view(torch.int16))
+               for a, c in zip((outs[0], xbs[0].flatten()),
+                               (outs[1], xbs[1].flatten()))) and \
+        torch.equal(masks[0], masks[1])
+    print(f"conv1 input path: fused out, mask, xb equal to pad + forward: "
+          f"{same}")
+    for name, f in (("pad kernel alone", pad), ("bf16 forward alone", fwd),
+                    ("pad + bf16 forward", parent),
+                    ("fp32 forward + copy", fused),
+                    ("fp32 forward, no copy", fused_no_copy),
+                    ("pad + bf16 forward", parent),
+                    ("fp32 forward + copy", fused)):
+        lo, med = bench(f, reps)
+        print(f"conv1 {name:24s} min {lo:7.4f}  median {med:7.4f} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-wg", type=int, nargs="*", default=[])
@@ -53,6 +110,10 @@ def main():
                          "collection with rocprofv3 --pmc")
     args = ap.parse_args()
     hook = getattr(_geops, "conv5_pool_nwg_nhwc", None)
+
+    if getattr(_geops, "conv5_pool_x32_nhwc", None) is not None \
+            and not args.once:
+        x32_ab(args.reps)
 
     for name, cir, co, h in SHAPES:
         torch.manual_seed(5)

@@ -7,8 +7,10 @@ in the format of profiles/*_steady.txt.
     python scripts/steady_profile.py DIR --title "..." > profiles/x.txt
 
 A step starts at each dispatch of the marker kernel (the 3->4 channel
-pad, the first kernel of a step). The table is the mean over the last
-STEPS complete steps before the last marker."""
+pad, the first kernel of a step; a build whose step has no pad kernel
+names another once-a-step kernel with --marker). The table is the mean
+over the last STEPS complete steps before the last marker; `spread` is
+the largest minus the smallest of a kernel's per-step times."""
 import argparse
 import collections
 import csv
@@ -49,17 +51,23 @@ def main():
     busy = sum(e - s for s, e, _ in win) / 1e6 / k
     cnt = collections.Counter()
     ms = collections.Counter()
+    per_step = collections.defaultdict(lambda: [0.0] * args.steps)
+    starts = [rows[i][0] for i in marks[-1 - args.steps:-1]]
     for s, e, name in win:
         cnt[name] += 1
         ms[name] += (e - s) / 1e6
+        step = sum(1 for t in starts if t <= s) - 1
+        per_step[name][step] += (e - s) / 1e6
     if args.title:
         print(args.title)
     print("steady state, mean of %d steps: wall %.3f ms/step, GPU-busy "
           "%.3f ms/step, %.1f dispatches/step"
           % (args.steps, wall, busy, len(win) / k))
-    print("%-100s %8s %9s" % ("kernel", "n/step", "ms/step"))
+    print("%-100s %8s %9s %8s" % ("kernel", "n/step", "ms/step", "spread"))
     for name, t in sorted(ms.items(), key=lambda kv: -kv[1]):
-        print("%-100s %8.1f %9.4f" % (name[:100], cnt[name] / k, t / k))
+        print("%-100s %8.1f %9.4f %8.4f"
+              % (name[:100], cnt[name] / k, t / k,
+                 max(per_step[name]) - min(per_step[name])))
 
 
 if __name__ == "__main__":

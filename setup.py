@@ -43,6 +43,9 @@ ext = CUDAExtension(
 # conv1c.hip (the CI = 1 conv stage) sums its four waves' slabs in a
 # stated order and is built the same way. bscselect.hip forms its keys with
 # one rounded multiply and two rounded additions (bsc_mom.h) and is too.
+# conv1x32.hip (the conv1 stage from the fp32 image) is too: its kernel is
+# the fp32 instantiation of the template in conv5_pool2.h, whose bf16
+# instantiation conv.hip keeps building as before.
 # The extension's flag list is one for all of its sources, so these are
 # compiled here, with the same flags plus the feature switch, and linked
 # into _geops as objects. They include no torch header.
@@ -50,10 +53,12 @@ NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
                      "geomx_amd/csrc/wiresparse.hip",
                      "geomx_amd/csrc/dgtencode.hip",
                      "geomx_amd/csrc/conv1c.hip",
-                     "geomx_amd/csrc/bscselect.hip"]
+                     "geomx_amd/csrc/bscselect.hip",
+                     "geomx_amd/csrc/conv1x32.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h",
                      "geomx_amd/csrc/bsc_mom.h",
-                     "geomx_amd/csrc/conv5_common.h"]
+                     "geomx_amd/csrc/conv5_common.h",
+                     "geomx_amd/csrc/conv5_pool2.h"]
 NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 ext.depends += NO_PK_F32_SOURCES + NO_PK_F32_DEPENDS
 
