@@ -27,6 +27,9 @@ def main():
     p = base_parser()
     p.add_argument("--compress", type=str, default=None,
                    choices=[None, "bsc", "fp16", "mpq", "dgt"])
+    p.add_argument("--lars", action="store_true",
+                   help="LBSGD with a layer-wise LARS trust ratio in place "
+                        "of sgd_mom")
     args = p.parse_args()
 
     parties = args.parties if topo_world() > 1 else 1
@@ -35,8 +38,10 @@ def main():
     device = topo.device
     torch.manual_seed(0)
     net = create_model("resnet50", num_classes=10).to(device)
-    trainer = GeoTrainer(net, cfg, topo,
-                         OptimizerSpec("sgd_mom", lr=args.learning_rate),
+    spec = OptimizerSpec("lbsgd", warmup_strategy="lars", momentum=0.9,
+                         lr=args.learning_rate) if args.lars \
+        else OptimizerSpec("sgd_mom", lr=args.learning_rate)
+    trainer = GeoTrainer(net, cfg, topo, spec,
                          mode="hips" if parties > 1 else "flat")
 
     class _KV:  # make_loaders only needs sharding info

@@ -6,7 +6,8 @@
 // boundary select),
 // convwrw2.hip (5x5 conv weight gradient, tr16 probes) and fc.hip
 // (NHWC-native first dense layer layout kernels: permuting weight casts,
-// transposing flatten).
+// transposing flatten), lars.hip (layer-wise LARS: segmented sums of squares
+// and the per-segment sgd update).
 //
 // Thin checked wrappers: dtype/contiguity/device checks, stream plumbing
 // (kernels run on the current torch stream so they order correctly with
@@ -60,6 +61,15 @@ void geops_signsgd_update(float*, const float*, float, float, float,
                           long long, hipStream_t);
 void geops_signum_update(float*, const float*, float*, float, float, float,
                          float, long long, hipStream_t);
+// lars.hip
+int geops_lars_tile();
+void geops_lars_sumsq(const float*, const float*, const long long*,
+                      const long long*, float*, float*, int, long long,
+                      long long, double, int, int, hipStream_t);
+void geops_lars_update(float*, const float*, float*, const long long*,
+                       const long long*, const float*, int, long long,
+                       long long, double, double, float, float, float, int,
+                       int, hipStream_t);
 // wirereduce.hip
 void geops_wire_sum_2bit(const void* const*, int, float*, long long, float,
                          bool, hipStream_t);
@@ -1469,6 +1479,95 @@ void rsp_adagrad_update(torch::Tensor w, torch::Tensor ids,
   launch_check("rsp_adagrad_update");
 }
 
+// -- layer-wise LARS (lars.hip) ---------------------------------------------
+// seg_off[S+1] cuts the n elements into S segments, tile_start[S+1] is the
+// prefix sum of ceil(len_s / LARS_TILE); ops builds and validates both on
+// the host (the kernels bound every tile by n once more). VEC = 4 needs
+// 16 B-aligned operands and offsets that are multiples of 4: `vec4` says
+// that the offsets are, the pointers are looked at here. n_wg: 0 = default
+// grid, > 0 that many workgroups (the tests' hook, as conv5_dgrad_nwg_nhwc).
+struct LarsArgs {
+  int S;
+  long long total, n;
+  int vec;
+};
+
+LarsArgs lars_check(const char* what, const torch::Tensor& w,
+                    std::initializer_list<const torch::Tensor*> same,
+                    const torch::Tensor& seg_off,
+                    const torch::Tensor& tile_start,
+                    const torch::Tensor& ratio, int64_t total, bool vec4,
+                    int64_t n_wg) {
+  check_rsp_f32(w, "w");
+  check_rsp_f32(ratio, "ratio");
+  check_rsp_i64(seg_off, "seg_off");
+  check_rsp_i64(tile_start, "tile_start");
+  bool aligned = ((uintptr_t)w.data_ptr() & 15) == 0;
+  for (const torch::Tensor* t : same) {
+    check_rsp_f32(*t, "g / mom");
+    check_same_numel(w, *t, "g / mom");
+    TORCH_CHECK(t->device() == w.device(), what, ": operands on one device");
+    aligned = aligned && ((uintptr_t)t->data_ptr() & 15) == 0;
+  }
+  const int64_t S = ratio.numel(), n = w.numel();
+  TORCH_CHECK(seg_off.numel() == S + 1 && tile_start.numel() == S + 1, what,
+              ": seg_off and tile_start hold one entry more than ratio");
+  TORCH_CHECK(seg_off.device() == w.device() &&
+                  tile_start.device() == w.device() &&
+                  ratio.device() == w.device(),
+              what, ": tables on w's device");
+  TORCH_CHECK(n <= INT32_MAX && S <= INT32_MAX, what, " serves n < 2^31");
+  // a tile holds at least one element, and every segment at most one
+  // partial tile
+  TORCH_CHECK(total >= 0 && total <= n &&
+                  total <= n / geops_lars_tile() + S,
+              what, ": tile count ", total, " does not fit n = ", n);
+  TORCH_CHECK(n_wg >= 0 && n_wg <= 65536, what, ": bad n_wg");
+  return LarsArgs{(int)S, (long long)total, (long long)n,
+                  (vec4 && aligned) ? 4 : 1};
+}
+
+void lars_sumsq(torch::Tensor w, torch::Tensor g, torch::Tensor seg_off,
+                torch::Tensor tile_start, torch::Tensor partials,
+                torch::Tensor ratio, int64_t total, double wd, bool vec4,
+                int64_t n_wg) {
+  const LarsArgs a = lars_check("lars_sumsq", w, {&g}, seg_off, tile_start,
+                                ratio, total, vec4, n_wg);
+  check_rsp_f32(partials, "partials");
+  TORCH_CHECK(((uintptr_t)partials.data_ptr() & 7) == 0 &&
+                  partials.numel() >= 2 * total,
+              "lars_sumsq: partials holds one 8 B-aligned pair per tile");
+  TORCH_CHECK(partials.device() == w.device(),
+              "lars_sumsq: workspace on w's device");
+  if (a.S == 0) return;
+  geops_lars_sumsq(w.data_ptr<float>(), g.data_ptr<float>(), i64p(seg_off),
+                   i64p(tile_start), partials.data_ptr<float>(),
+                   ratio.data_ptr<float>(), a.S, a.total, a.n, wd, a.vec,
+                   (int)n_wg, cur_stream());
+  launch_check("lars_sumsq");
+}
+
+// mom empty (torch.Tensor()): plain sgd, as for dcasgd's mom
+void lars_update(torch::Tensor w, torch::Tensor g, torch::Tensor mom,
+                 torch::Tensor seg_off, torch::Tensor tile_start,
+                 torch::Tensor ratio, int64_t total, double lr, double lbmult,
+                 double momentum, double wd, double rescale, bool vec4,
+                 int64_t n_wg) {
+  const bool has_mom = mom.defined() && mom.numel() > 0;
+  const LarsArgs a =
+      has_mom ? lars_check("lars_update", w, {&g, &mom}, seg_off, tile_start,
+                           ratio, total, vec4, n_wg)
+              : lars_check("lars_update", w, {&g}, seg_off, tile_start, ratio,
+                           total, vec4, n_wg);
+  if (a.total == 0) return;
+  geops_lars_update(w.data_ptr<float>(), g.data_ptr<float>(),
+                    has_mom ? mom.data_ptr<float>() : nullptr, i64p(seg_off),
+                    i64p(tile_start), ratio.data_ptr<float>(), a.S, a.total,
+                    a.n, lr, lbmult, (float)momentum, (float)wd,
+                    (float)rescale, a.vec, (int)n_wg, cur_stream());
+  launch_check("lars_update");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1545,6 +1644,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adagrad_update", &adagrad_update);
   m.def("signsgd_update", &signsgd_update);
   m.def("signum_update", &signum_update);
+  m.def("lars_sumsq", &lars_sumsq);
+  m.def("lars_update", &lars_update);
+  // elements per tile of the LARS kernels
+  m.attr("LARS_TILE") = geops_lars_tile();
   m.def("rsp_merge", &rsp_merge);
   m.def("rsp_scatter", &rsp_scatter);
   m.def("rsp_sgd_update", &rsp_sgd_update);

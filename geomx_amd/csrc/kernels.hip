@@ -16,19 +16,9 @@
 
 #include <cstdint>
 #include "bsc_mom.h"
+#include "geops_grid.h"
 #include "optim_rules.h"
 #include "wire_codec.h"
-
-#define GEOPS_THREADS 256
-#define GEOPS_MAX_BLOCKS 2048
-
-static inline int geops_blocks(long long work, int per_thread = 1) {
-  long long b = (work + (long long)GEOPS_THREADS * per_thread - 1) /
-                ((long long)GEOPS_THREADS * per_thread);
-  if (b < 1) b = 1;
-  if (b > GEOPS_MAX_BLOCKS) b = GEOPS_MAX_BLOCKS;
-  return (int)b;
-}
 
 // ---------------------------------------------------------------------------
 // 2bit quantization (gradient_compression-inl.h:40-139 semantics)

@@ -23,6 +23,7 @@ from .. import ops
 @dataclasses.dataclass
 class OptimizerSpec:
     name: str = "sgd"   # sgd|sgd_mom|adam|dcasgd|rmsprop|adagrad|signsgd|signum
+                        # |lbsgd
     lr: float = 0.01
     momentum: float = 0.9
     beta1: float = 0.9
@@ -40,11 +41,29 @@ class OptimizerSpec:
                                  # the state of absent rows untouched
                                  # (MXNet lazy_update; its default is True,
                                  # ours False keeps dense-equivalent results)
+    # lbsgd only (reference LBSGD, optimizer.py:681-868). 'lars' scales each
+    # layer's rate by its trust ratio; the other three are warm-up schedules
+    # of the rate from 1 to batch_scale over warmup_epochs epochs. The
+    # reference's macro-batch cumulation is not built: batch_scale is the
+    # warm-up ceiling only (docs/api.md).
+    warmup_strategy: str = "linear"   # linear|power2|sqrt|lars
+    warmup_epochs: int = 5
+    batch_scale: float = 1
+    updates_per_epoch: int = 32
+    begin_epoch: int = 0
 
     def validate(self):
         if self.name not in ("sgd", "sgd_mom", "adam", "dcasgd", "rmsprop",
-                             "adagrad", "signsgd", "signum"):
+                             "adagrad", "signsgd", "signum", "lbsgd"):
             raise ValueError(f"unknown optimizer {self.name!r}")
+        if self.warmup_strategy not in ("linear", "power2", "sqrt", "lars"):
+            raise ValueError(
+                f"unknown warmup_strategy {self.warmup_strategy!r}")
+        if self.warmup_epochs < 0 or self.updates_per_epoch < 0 \
+                or self.begin_epoch < 0 or self.batch_scale <= 0:
+            raise ValueError("warmup_epochs, updates_per_epoch and "
+                             "begin_epoch must not be negative, batch_scale "
+                             "must be positive")
         return self
 
 
@@ -67,6 +86,8 @@ class ServerOptimizer:
         self.step_count: Dict[object, int] = {}
         # per-key zeroed dense gradient for update_rows' dense fallback
         self._dense_grad: Dict[object, torch.Tensor] = {}
+        # lbsgd without `segments`: the offsets [0, n] per (n, device)
+        self._whole: Dict[object, torch.Tensor] = {}
 
     def _get_state(self, key, w: torch.Tensor) -> Dict[str, torch.Tensor]:
         st = self.state.get(key)
@@ -74,6 +95,9 @@ class ServerOptimizer:
             st = {}
             if self.spec.name == "sgd_mom":
                 st["mom"] = torch.zeros_like(w)
+            elif self.spec.name == "lbsgd":
+                if self.spec.momentum != 0.0:   # as the reference: no
+                    st["mom"] = torch.zeros_like(w)  # state without momentum
             elif self.spec.name == "adam":
                 st["m"] = torch.zeros_like(w)
                 st["v"] = torch.zeros_like(w)
@@ -90,10 +114,15 @@ class ServerOptimizer:
         return st
 
     def update(self, key, w: torch.Tensor, grad: torch.Tensor,
-               rescale: Optional[float] = None):
-        """Apply one fused update of `w` (fp32, flat) with aggregated grad."""
+               rescale: Optional[float] = None,
+               segments: Optional[torch.Tensor] = None):
+        """Apply one fused update of `w` (fp32, flat) with aggregated grad.
+        `segments` (lbsgd with 'lars' only; ignored otherwise) is the int64
+        tensor of S+1 ascending element offsets that cut `w` into layers;
+        None is one layer, the whole of `w`."""
         s = self.spec
         rs = s.rescale_grad if rescale is None else rescale
+        raw = grad   # lbsgd takes its norms before rescale and clip
         if s.clip_gradient is not None:
             # reference clips the RESCALED gradient, so fold the scale
             # in here and hand the kernels rs=1
@@ -121,6 +150,29 @@ class ServerOptimizer:
             ops.signsgd_update(w, grad, s.lr, s.wd, rs)
         elif s.name == "signum":
             ops.signum_update(w, grad, st["mom"], s.lr, s.momentum, s.wd, rs)
+        elif s.name == "lbsgd":
+            self._lbsgd(w, grad, raw, st.get("mom"), rs, t, segments)
+
+    def _lbsgd(self, w, grad, raw, mom, rs, t, segments):
+        s = self.spec
+        if s.warmup_strategy == "lars":
+            if segments is None:
+                ck = (w.numel(), w.device)
+                segments = self._whole.get(ck)
+                if segments is None:
+                    segments = self._whole[ck] = torch.tensor(
+                        [0, w.numel()], dtype=torch.int64, device=w.device)
+            ops.lbsgd_update(w, grad, mom, segments, s.lr, s.momentum, s.wd,
+                             rs, 1.0, g_norm=None if raw is grad else raw)
+            return
+        # a schedule: the host's multiplier on the plain kernels
+        lr = s.lr * ops.reference.lbsgd_lbmult(
+            t + s.begin_epoch * s.updates_per_epoch, s.warmup_strategy,
+            s.warmup_epochs, s.updates_per_epoch, s.batch_scale)
+        if mom is not None:
+            ops.sgd_mom_update(w, grad, mom, lr, s.momentum, s.wd, rs)
+        else:
+            ops.sgd_update(w, grad, lr, s.wd, rs)
 
     _ROW_KERNELS = ("sgd", "sgd_mom", "adam", "adagrad")
 

@@ -547,6 +547,131 @@ def dcasgd_update(w, g, prev_w, mom, lr, lamda=0.04, momentum=0.0, wd=0.0,
 
 
 # ---------------------------------------------------------------------------
+# Layer-wise LARS (LBSGD, warmup_strategy='lars') over a flat bucket whose
+# layers are the segments [seg_off[s], seg_off[s+1]): k_lars_sumsq writes the
+# tiles' sums of squares, k_lars_ratio the trust ratios, k_lars_update
+# applies sgd / sgd-momentum with lr * ratio[s]. Three launches and no host
+# wait, whatever the number of segments.
+# ---------------------------------------------------------------------------
+
+# elements per tile of the LARS kernels (None without the extension)
+LARS_TILE = getattr(_geops, "LARS_TILE", None)
+
+_lars_table_cache: dict = {}
+_lars_ws_cache: dict = {}
+
+
+def _lars_tables(seg_off: torch.Tensor, n: int, device):
+    """(seg_off, tile_start, tile count, offsets all multiples of 4) on
+    `device` for one offsets tensor: read and checked on the host ONCE per
+    distinct tensor (storage, length and version), then cached. The cache
+    keeps the tensor alive, so its address names it."""
+    ck = (seg_off.device, seg_off.data_ptr(), seg_off.numel(),
+          seg_off._version, n, device)
+    hit = _lars_table_cache.get(ck)
+    if hit is None:
+        if seg_off.dtype != torch.int64 or seg_off.dim() != 1 \
+                or seg_off.numel() < 1:
+            raise ValueError("seg_off is a 1-d int64 tensor of S+1 offsets")
+        offs = seg_off.tolist()
+        if offs[0] != 0 or offs[-1] != n \
+                or any(b < a for a, b in zip(offs[:-1], offs[1:])):
+            raise ValueError("seg_off must ascend from 0 to w.numel() = %d"
+                             % n)
+        tile_start = [0]
+        for a, b in zip(offs[:-1], offs[1:]):
+            tile_start.append(tile_start[-1] + (b - a + LARS_TILE - 1)
+                              // LARS_TILE)
+        if len(_lars_table_cache) > 64:
+            _lars_table_cache.clear()
+        hit = _lars_table_cache[ck] = (
+            seg_off.to(device).contiguous(),
+            torch.tensor(tile_start, dtype=torch.int64).to(device),
+            tile_start[-1], all(o % 4 == 0 for o in offs), seg_off)
+    return hit[:4]
+
+
+def _lars_workspace(device, tiles: int) -> torch.Tensor:
+    """The tiles' (sum w^2, sum g^2) pairs per (device, tile count): one
+    call at a time uses it (calls on one stream do)."""
+    ck = (device, tiles)
+    ws = _lars_ws_cache.get(ck)
+    if ws is None:
+        if len(_lars_ws_cache) > 64:
+            _lars_ws_cache.clear()
+        ws = _lars_ws_cache[ck] = torch.empty(
+            2 * max(tiles, 1), dtype=torch.float32, device=device)
+    return ws
+
+
+def _lars_served(*operands) -> bool:
+    """What the LARS kernels serve: contiguous fp32 GPU operands of fewer
+    than 2^31 elements (any alignment: VEC = 1 takes what VEC = 4 cannot)."""
+    return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               and t.numel() < 2 ** 31 for t in operands)
+
+
+def lars_ratio(w: torch.Tensor, g: torch.Tensor, seg_off: torch.Tensor,
+               wd: float = 0.0, out: Optional[torch.Tensor] = None,
+               n_wg: int = 0) -> torch.Tensor:
+    """fp32 [S] trust ratios of LBSGD's 'lars' strategy, one per segment of
+    the flat `w` / `g` (ref.lars_ratio; empty segments get 0.01). On the GPU
+    two launches, reproducible bit for bit and without a host wait once the
+    tables of `seg_off` are cached (the first call with a new `seg_off`
+    reads it on the host). `n_wg` is the tests' grid hook (0 = default)."""
+    if _on_gpu(w, g) and _lars_served(w, g):
+        gk = _require_native()
+        seg, tile_start, tiles, vec4 = _lars_tables(seg_off, w.numel(),
+                                                    w.device)
+        S = seg.numel() - 1
+        if out is None:
+            out = torch.empty(S, dtype=torch.float32, device=w.device)
+        gk.lars_sumsq(w.view(-1), g.view(-1), seg, tile_start,
+                      _lars_workspace(w.device, tiles), out, tiles, wd, vec4,
+                      n_wg)
+        return out
+    r = ref.lars_ratio(w, g, seg_off, wd)
+    if out is not None:
+        out.copy_(r)
+        return out
+    return r
+
+
+def lbsgd_update(w, g, mom, seg_off, lr, momentum=0.0, wd=0.0, rescale=1.0,
+                 lbmult=1.0, ratio_out: Optional[torch.Tensor] = None,
+                 g_norm: Optional[torch.Tensor] = None, n_wg: int = 0):
+    """One LBSGD 'lars' step of the flat bucket `w`: segment s is updated
+    by sgd (momentum == 0: no state, `mom` may be None) or sgd-momentum with
+    the rate lr * ratio[s] * lbmult (ref.lbsgd_update). The ratios are taken
+    of `g` before `rescale`, or of `g_norm` when given (the unclipped
+    gradient), and returned (in `ratio_out` when given). On the GPU this is
+    three launches and no host wait."""
+    use_mom = momentum != 0.0
+    if use_mom and mom is None:
+        raise ValueError("lbsgd_update with momentum needs its state")
+    gn = g if g_norm is None else g_norm
+    operands = (w, g, gn) + ((mom,) if use_mom else ())
+    if _on_gpu(*operands) and _lars_served(*operands):
+        gk = _require_native()
+        wf = _flat_inplace(w, "w")
+        ratio = lars_ratio(wf, gn, seg_off, wd, out=ratio_out, n_wg=n_wg)
+        seg, tile_start, tiles, vec4 = _lars_tables(seg_off, wf.numel(),
+                                                    w.device)
+        gk.lars_update(wf, g.view(-1),
+                       _flat_inplace(mom, "mom") if use_mom
+                       else torch.Tensor(),
+                       seg, tile_start, ratio, tiles, lr, lbmult, momentum,
+                       wd, rescale, vec4, n_wg)
+        return ratio
+    ratio = ref.lbsgd_update(w, g, mom, seg_off, lr, momentum, wd, rescale,
+                             lbmult, g_norm=g_norm)
+    if ratio_out is not None:
+        ratio_out.copy_(ratio)
+        return ratio_out
+    return ratio
+
+
+# ---------------------------------------------------------------------------
 # Row-sparse push: duplicate merge, row scatter, row-indexed updates.
 # Tables, states and merged rows are 2-d [rows][width] fp32; ids are int64.
 # Ids outside [0, rows) (the -1 padding included) are skipped.

@@ -402,6 +402,73 @@ def sgd_mom_update(w: torch.Tensor, g: torch.Tensor, mom: torch.Tensor,
     w.add_(mom)
 
 
+def lbsgd_lbmult(nup: int, strategy: str = "linear", warmup_epochs: int = 5,
+                 updates_per_epoch: int = 32, batch_scale: float = 1) -> float:
+    """LBSGD's warm-up multiplier of the learning rate after `nup` updates
+    (optimizer.py:754-774, _get_lbmult); 'lars' has none (1.0)."""
+    nwup = warmup_epochs * updates_per_epoch
+    maxmult = float(batch_scale)
+    if nup >= nwup:
+        return maxmult
+    if nwup <= 1:
+        return 1.0
+    if strategy == "linear":
+        return 1.0 + (maxmult - 1) * nup / nwup
+    if strategy == "power2":
+        return 1.0 + (maxmult - 1) * (nup * nup) / (nwup * nwup)
+    if strategy == "sqrt":
+        return 1.0 + (maxmult - 1) * math.sqrt(float(nup) / nwup)
+    return 1.0
+
+
+def lars_ratio(w: torch.Tensor, g: torch.Tensor, seg_off: torch.Tensor,
+               wd: float = 0.0, dtype=torch.float32) -> torch.Tensor:
+    """Layer-wise trust ratio of LBSGD (optimizer.py:776-792, _get_lars) for
+    each segment [seg_off[s], seg_off[s+1]) of the flat w and g:
+    sqrt(|w|^2 / (|g|^2 + wd |w|^2 + 1e-18)) clamped to [0.01, 100], the
+    sums in float64. `dtype=torch.float64` keeps the unrounded value."""
+    offs = seg_off.tolist()
+    wf, gf = w.reshape(-1), g.reshape(-1)
+    out = []
+    for a, b in zip(offs[:-1], offs[1:]):
+        w2 = wf[a:b].double().square().sum().item()
+        g2 = gf[a:b].double().square().sum().item()
+        lars = math.sqrt(w2 / (g2 + wd * w2 + 1e-18))
+        if lars < 0.01:
+            lars = 0.01
+        elif lars > 100:
+            lars = 100
+        out.append(lars)
+    return torch.tensor(out, dtype=torch.float64, device=w.device).to(dtype)
+
+
+def lbsgd_update(w: torch.Tensor, g: torch.Tensor,
+                 mom: Optional[torch.Tensor], seg_off: torch.Tensor,
+                 lr: float, momentum: float = 0.0, wd: float = 0.0,
+                 rescale: float = 1.0, lbmult: float = 1.0,
+                 ratio: Optional[torch.Tensor] = None,
+                 g_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LBSGD with warmup_strategy='lars' (optimizer.py:827-868) on every
+    segment: sgd (momentum == 0, no state) or sgd-momentum with the rate
+    lr * ratio[s] * lbmult. The ratio is that of the gradient as given,
+    before `rescale`; `g_norm` is the gradient to take it of when `g` is not
+    that one (a clipped gradient), `ratio` replaces the computation. Returns
+    the fp32 ratios used."""
+    if ratio is None:
+        ratio = lars_ratio(w, g if g_norm is None else g_norm, seg_off, wd)
+    offs = seg_off.tolist()
+    wf, gf = w.view(-1), g.reshape(-1)
+    mf = mom.view(-1) if mom is not None and momentum != 0.0 else None
+    for s, (a, b) in enumerate(zip(offs[:-1], offs[1:])):
+        lr_s = lr * float(ratio[s]) * lbmult
+        if mf is not None:
+            sgd_mom_update(wf[a:b], gf[a:b], mf[a:b], lr_s, momentum, wd,
+                           rescale)
+        else:
+            sgd_update(wf[a:b], gf[a:b], lr_s, wd, rescale)
+    return ratio
+
+
 def adam_update(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                 v: torch.Tensor, t: int, lr: float, beta1: float = 0.9,
                 beta2: float = 0.999, eps: float = 1e-8, wd: float = 0.0,

@@ -52,7 +52,7 @@ from ..topology import Topology
 class _Bucket:
     __slots__ = ("params", "flat", "param_flat", "views", "ready", "expected",
                  "work", "index", "bsc_u", "bsc_v", "dgt", "res2bit",
-                 "wan_buf", "wan_work", "wan_ready", "clear")
+                 "wan_buf", "wan_work", "wan_ready", "clear", "seg_off")
 
     def __init__(self, index: int):
         self.index = index
@@ -63,6 +63,9 @@ class _Bucket:
         # what zero_grad() fills: the maximal contiguous ranges of
         # `flat` outside every gradient-sink span
         self.clear: List[torch.Tensor] = []
+        # lbsgd: offsets of the parameters in the bucket (one LARS layer
+        # each, its alignment padding included), else None
+        self.seg_off: Optional[torch.Tensor] = None
         self.ready = 0
         self.expected = 0
         self.work = None
@@ -197,6 +200,7 @@ class GeoTrainer:
                                        device=self.device)
             off = 0
             lo = 0   # start of the current run of non-sink elements
+            offs = [0]
             for p in b.params:
                 n = p.numel()
                 view = _alias_view(b.flat, off, p)
@@ -217,8 +221,14 @@ class GeoTrainer:
                         b.clear.append(b.flat[lo:off])
                     lo = off + n   # the span's own padding is cleared
                 off += aligned(n)
+                offs.append(off)
             if total > lo:
                 b.clear.append(b.flat[lo:total])
+            if self.spec.name == "lbsgd":
+                # the padding is zero in param_flat, flat and the state and
+                # stays zero, so it changes no norm
+                b.seg_off = torch.tensor(offs, dtype=torch.int64,
+                                         device=self.device)
 
     def _register_hooks(self):
         self._hook_handles = []
@@ -351,7 +361,7 @@ class GeoTrainer:
         self._settle_grads()
         for b in self.buckets:
             self.server_opt.update(("bucket", b.index), b.param_flat,
-                                   b.flat, rescale=rs)
+                                   b.flat, rescale=rs, segments=b.seg_off)
             b.ready = 0
         self._settled = False   # the step is over
 
@@ -383,7 +393,7 @@ class GeoTrainer:
                     comm.broadcast(apply_buf, src=topo.leader_rank,
                                    group=topo.party_group)
                 self.server_opt.update(("bucket", b.index), b.param_flat,
-                                       apply_buf)
+                                       apply_buf, segments=b.seg_off)
             # 2) launch this step's WAN exchange from a snapshot
             if topo.is_leader:
                 if ctype == "fp16":

@@ -276,6 +276,66 @@ def wire_sparse_rows(n, iters, report, results):
         torch.cuda.empty_cache()
 
 
+def lars_rows(n, iters, report, results):
+    """LBSGD 'lars' step (k_lars_sumsq + k_lars_update) at n elements, with
+    one segment and with the flagship bucket's segments (the geomx_cnn
+    parameters on 64-element boundaries, repeated to fill n), against
+    k_sgd_mom_update and the PyTorch expression of the rule (two
+    vector_norm and one update per segment) on the same buffers, in 5
+    alternating windows. Necessary bytes: 8n for the sums, 20n for the
+    update, as k_sgd_mom_update."""
+    from geomx_amd.models import create_model
+    dev = "cuda:0"
+    iters = max(5, iters // 5)
+    w = torch.randn(n, device=dev)
+    g = torch.randn(n, device=dev)
+    m = torch.zeros(n, device=dev)
+    lens = [(p.numel() + 63) // 64 * 64
+            for p in create_model("geomx_cnn", image_size=224).parameters()]
+    offs = [0]
+    while offs[-1] < n:
+        offs.append(min(n, offs[-1] + lens[(len(offs) - 1) % len(lens)]))
+    layouts = {"1 seg": [0, n], "%d segs" % (len(offs) - 1): offs}
+
+    def torch_rule(bounds):
+        for a, b in zip(bounds[:-1], bounds[1:]):
+            w2 = torch.linalg.vector_norm(w[a:b]) ** 2
+            g2 = torch.linalg.vector_norm(g[a:b]) ** 2
+            lr = 0.01 * torch.sqrt(w2 / (g2 + 1e-18)).clamp(0.01, 100.0)
+            m[a:b].mul_(0.9).sub_(lr * g[a:b])
+            w[a:b].add_(m[a:b])
+
+    def sgd_mom():
+        ops.sgd_mom_update(w, g, m, 0.01, 0.9)
+
+    for name, bounds in layouts.items():
+        seg = torch.tensor(bounds, dtype=torch.int64, device=dev)
+        ratio = ops.lars_ratio(w, g, seg)
+        tabs = ops._lars_tables(seg, n, w.device)
+        ta, tb = window_pair(lambda: ops.lars_ratio(w, g, seg, out=ratio),
+                             lambda: ops._geops.lars_update(
+                                 w, g, m, tabs[0], tabs[1], ratio, tabs[2],
+                                 0.01, 1.0, 0.9, 0.0, 1.0, tabs[3], 0),
+                             iters, reps=5)
+        tl, ts = window_pair(
+            lambda: ops.lbsgd_update(w, g, m, seg, 0.01, 0.9), sgd_mom, iters,
+            reps=5)
+        # the eager rule is slow with many segments: one window of 2 calls
+        tt, _ = window_pair(lambda: torch_rule(bounds), sgd_mom, 2, reps=1)
+        for row, nbytes, t in (("k_lars_sumsq", 8 * n, ta),
+                               ("k_lars_update", 20 * n, tb),
+                               ("lbsgd_update", 28 * n, tl),
+                               ("sgd_mom_update", 20 * n, ts),
+                               ("torch lars rule", 28 * n, tt)):
+            t = sorted(t)
+            med = t[len(t) // 2]
+            report("%s (%s)" % (row, name), nbytes, med)
+            results[-1]["windows_ms"] = [round(x * 1e3, 4) for x in t]
+        ml, ms = sorted(tl)[2], sorted(ts)[2]
+        results[-1]["lbsgd_over_sgd_mom"] = round(ml / ms, 3)
+        print("%24s lbsgd / sgd_mom = %.3f" % ("", ml / ms))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 26)  # 64M fp32 = 256 MB
@@ -287,6 +347,8 @@ def main():
                     help="only the Bi-Sparse boundary rows, chain and kernel")
     ap.add_argument("--only-dgt", action="store_true",
                     help="only the fused DGT encode rows")
+    ap.add_argument("--only-lars", action="store_true",
+                    help="only the LBSGD 'lars' rows")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     assert ops.native_available(), ops.native_error()
@@ -325,6 +387,11 @@ def main():
     if args.only_dgt:
         del g
         dgt_encode_rows(n, args.iters, report, results)
+        dump()
+        return
+    if args.only_lars:
+        del g
+        lars_rows(n, args.iters, report, results)
         dump()
         return
 
@@ -437,6 +504,7 @@ def main():
     wire_reduce_rows(n, args.iters, report, results)
     wire_sparse_rows(n, args.iters, report, results)
     dgt_encode_rows(n, args.iters, report, results)
+    lars_rows(n, args.iters, report, results)
     dump()
 
 
