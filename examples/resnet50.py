@@ -8,7 +8,8 @@ GEOMX_* env)."""
 
 import torch
 
-from common import base_parser, topo_world, make_loaders, eval_acc
+from common import (TableInput, base_parser, eval_acc, input_table,
+                    make_loaders, topo_world)
 
 import os
 import sys
@@ -37,7 +38,10 @@ def main():
     topo = init_topology(parties)
     device = topo.device
     torch.manual_seed(0)
-    net = create_model("resnet50", num_classes=10).to(device)
+    net = create_model("resnet50", num_classes=10)
+    if args.uint8_input:   # the stem has no table of its own
+        net = TableInput(input_table(args), net)
+    net = net.to(device)
     spec = OptimizerSpec("lbsgd", warmup_strategy="lars", momentum=0.9,
                          lr=args.learning_rate) if args.lars \
         else OptimizerSpec("sgd_mom", lr=args.learning_rate)

@@ -39,6 +39,13 @@
 // wait in registers through it. Each staged row ends in zero pairs that
 // cover everything a clamped or last tile reads past the row; rows past
 // the image are zero.
+//
+// A uint8 input comes with a value table, bf16 [256], that the workgroup
+// copies into LDS once: byte v stands for tab[v], the bits cf2bf gives
+// for the fp32 image table[x] when the host rounded the fp32 table to
+// bf16. A pixel pair is then 2 bytes of global traffic (one ushort load)
+// and two ds_read_u16 on the way into the row image; everything behind
+// the row image is the same for the three input types.
 
 #include <hip/hip_runtime.h>
 
@@ -50,20 +57,58 @@
                          // so the rows one read touches sit 16 banks apart
 
 // One pair of adjacent pixels as the input holds it, and as bf16 x 2 (the
-// left pixel in the low half).
+// left pixel in the low half). `tab` is the LDS byte address of the value
+// table, read by the uint8 form only.
 template <typename TIN> struct PixPair;
 template <> struct PixPair<float> {
   typedef float2 raw;
   static __device__ __forceinline__ raw zero() { return make_float2(0, 0); }
-  static __device__ __forceinline__ unsigned pack(raw v) {
+  static __device__ __forceinline__ raw ld(const float* p) {
+    return *reinterpret_cast<const raw*>(p);
+  }
+  static __device__ __forceinline__ unsigned pack(raw v, unsigned) {
     return (unsigned)cf2bf(v.x) | ((unsigned)cf2bf(v.y) << 16);
   }
 };
 template <> struct PixPair<bf16_t> {
   typedef unsigned raw;
   static __device__ __forceinline__ raw zero() { return 0u; }
-  static __device__ __forceinline__ unsigned pack(raw v) { return v; }
+  static __device__ __forceinline__ raw ld(const bf16_t* p) {
+    return *reinterpret_cast<const raw*>(p);
+  }
+  static __device__ __forceinline__ unsigned pack(raw v, unsigned) {
+    return v;
+  }
 };
+// A pair past the image stages as zero bits, which tab[0] need not be: a
+// loaded pair carries bit 16 and zero() does not.
+template <> struct PixPair<uint8_t> {
+  typedef unsigned raw;
+  static __device__ __forceinline__ raw zero() { return 0u; }
+  static __device__ __forceinline__ raw ld(const uint8_t* p) {
+    return 0x10000u | *reinterpret_cast<const unsigned short*>(p);
+  }
+  static __device__ __forceinline__ unsigned pack(raw v, unsigned tab) {
+    typedef const __attribute__((address_space(3))) unsigned short* lds_u16;
+    const unsigned lo = *(lds_u16)(uintptr_t)(tab + (v & 0xFFu) * 2);
+    const unsigned hi = *(lds_u16)(uintptr_t)(tab + ((v >> 8) & 0xFFu) * 2);
+    return (v >> 16) ? (lo | (hi << 16)) : 0u;
+  }
+};
+constexpr int C1_TAB = 256;   // table entries
+
+// The uint8 forms' table into LDS, once per workgroup; the barrier puts
+// it ahead of the first lookups. Nothing for the other input types.
+template <typename TIN>
+__device__ __forceinline__ void c1_tab_load(bf16_t* lds_tab,
+                                            const bf16_t* __restrict__ tab) {
+  if constexpr (sizeof(TIN) == 1) {
+    for (int t = threadIdx.x; t < C1_TAB / 2; t += C1_THREADS)
+      reinterpret_cast<unsigned*>(lds_tab)[t] =
+          reinterpret_cast<const unsigned*>(tab)[t];
+    __syncthreads();
+  }
+}
 
 // Eight pixels from pixel s of a row image as one MFMA operand: `a` is
 // the LDS byte address of dword s >> 1, `sh` = (s & 1) * 2.
@@ -106,16 +151,16 @@ struct C1Stage {
     for (int i = 0; i < NIT; ++i) {
       v[i] = PixPair<TIN>::zero();
       if (row[i] >= 0 && h0 + row[i] < H && 2 * col[i] < W)
-        v[i] = *reinterpret_cast<const raw*>(
+        v[i] = PixPair<TIN>::ld(
             x + ((n * H + (h0 + row[i])) * (long long)W + 2 * col[i]));
     }
   }
-  __device__ __forceinline__ void write(char* img) const {
+  __device__ __forceinline__ void write(char* img, unsigned tab) const {
 #pragma unroll
     for (int i = 0; i < NIT; ++i)
       if (row[i] >= 0)
         *reinterpret_cast<unsigned*>(img + row[i] * C1_PITCH + col[i] * 4) =
-            PixPair<TIN>::pack(v[i]);
+            PixPair<TIN>::pack(v[i], tab);
   }
 };
 
@@ -150,7 +195,8 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_pool(
     const float* __restrict__ bias,      // [16] or nullptr
     bf16_t* __restrict__ out,            // [N][Hop][Wop][16]
     uint8_t* __restrict__ mask,          // [N*Hop*Wop*16]
-    int Nn, int H, int W) {
+    int Nn, int H, int W,
+    const bf16_t* __restrict__ tab) {    // uint8 form: [256]
   constexpr int CO = 16;
   constexpr int ROWS = 4;                 // conv rows per block
   constexpr int NROW = ROWS + 4;
@@ -161,6 +207,10 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_pool(
   static_assert(MAXRW * 4 <= C1_PITCH, "row and zero tail fit the pitch");
   static_assert(MAXU * 4 * 16 >= C1_MAXW - 4, "tiles cover the row");
   __shared__ __attribute__((aligned(16))) char lds_rows[2 * IMG];
+  __shared__ __attribute__((aligned(16))) bf16_t
+      lds_tab[sizeof(TIN) == 1 ? C1_TAB : 2];
+  c1_tab_load<TIN>(lds_tab, tab);
+  const unsigned tab0 = lds_addr(lds_tab);
 
   const int lane = threadIdx.x & 63;
   const int p = lane & 15;
@@ -228,7 +278,7 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_pool(
   long long pn = 0;
   int phb = 0, pnpr = 0;
   for (; blk < n_blocks; blk += n_wg, img ^= 1) {
-    st.write(lds_rows + img * IMG);
+    st.write(lds_rows + img * IMG, tab0);
     __syncthreads();
     flush(pn, phb, pnpr);
     if (blk + n_wg < n_blocks) load(blk + n_wg);
@@ -314,7 +364,8 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_wrw(
                                        // pooled [N][Ho/2][Wo/2][16]
     const uint8_t* __restrict__ mask,  // UNPOOL: argmax codes, as g
     float* __restrict__ part,          // [n_wg][32][16]
-    int Nn, int H, int W) {
+    int Nn, int H, int W,
+    const bf16_t* __restrict__ tab) {  // uint8 form: [256]
   constexpr int NROW_A = 2 + 4;
   constexpr int WMAX = (C1_MAXW - 4) / 32;         // 7 K windows
   constexpr int PB = WMAX * 1024;                  // gout row: 32 B / pixel
@@ -328,6 +379,10 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_wrw(
   static_assert(B_OFF % 16 == 0 && 4 * 512 * 4 <= 2 * PB,
                 "gout image aligned; the slab reduction fits in it");
   __shared__ __attribute__((aligned(16))) char lds_all[ONES + 64];
+  __shared__ __attribute__((aligned(16))) bf16_t
+      lds_tab[sizeof(TIN) == 1 ? C1_TAB : 2];
+  c1_tab_load<TIN>(lds_tab, tab);
+  const unsigned tab0 = lds_addr(lds_tab);
 
   const int lane = threadIdx.x & 63;
   const int q = lane >> 4;
@@ -388,7 +443,7 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_wrw(
     }
   };
   auto write = [&]() {
-    st.write(lds_all);
+    st.write(lds_all, tab0);
     if constexpr (UNPOOL) {
       pooled_write<NIT_P, C1_THREADS, 1, B_OFF, 0, PB>(lds_all, Wn, gq, mq);
     } else {
@@ -475,45 +530,58 @@ __global__ __launch_bounds__(C1_THREADS) void k_conv5c1_wrw(
 
 // ---------------------------------------------------------------------
 // Launchers. Both kernels serve even W from 6 to C1_MAXW; the forward
-// and the pooled wrw also need an even Ho. n_wg >= 1 is the grid. Return
-// 0, or -1 outside the served table.
+// and the pooled wrw also need an even Ho. x_kind says what x holds: 0
+// bf16, 1 fp32, 2 uint8 with its table `tab` (bf16 [256], 4 B aligned;
+// null for the other kinds). n_wg >= 1 is the grid. Return 0, or -1
+// outside the served table.
 // ---------------------------------------------------------------------
+static bool c1_kind_ok(int x_kind, const bf16_t* tab) {
+  if (x_kind == 2) return tab && ((uintptr_t)tab & 3) == 0;
+  return (x_kind == 0 || x_kind == 1) && !tab;
+}
+
 extern "C" {
 
-int geops_conv5c1_pool(const void* x, int x_is_fp32, const bf16_t* w_frags,
-                       const float* bias, bf16_t* out, uint8_t* mask, int Nn,
-                       int H, int W, int n_wg, hipStream_t s) {
+int geops_conv5c1_pool(const void* x, int x_kind, const bf16_t* tab,
+                       const bf16_t* w_frags, const float* bias, bf16_t* out,
+                       uint8_t* mask, int Nn, int H, int W, int n_wg,
+                       hipStream_t s) {
   if (Nn < 1 || H < 6 || W < 6 || W > C1_MAXW || (W & 1) || (H & 1) ||
-      n_wg < 1)
+      n_wg < 1 || !c1_kind_ok(x_kind, tab))
     return -1;
-  if (x_is_fp32)
-    hipLaunchKernelGGL((k_conv5c1_pool<float>), dim3(n_wg), dim3(C1_THREADS),
-                       0, s, (const float*)x, w_frags, bias, out, mask, Nn, H,
-                       W);
-  else
-    hipLaunchKernelGGL((k_conv5c1_pool<bf16_t>), dim3(n_wg),
-                       dim3(C1_THREADS), 0, s, (const bf16_t*)x, w_frags,
-                       bias, out, mask, Nn, H, W);
+#define C1POOL(TIN_)                                                       \
+  hipLaunchKernelGGL((k_conv5c1_pool<TIN_>), dim3(n_wg), dim3(C1_THREADS), \
+                     0, s, (const TIN_*)x, w_frags, bias, out, mask, Nn, H, \
+                     W, tab)
+  if (x_kind == 2) C1POOL(uint8_t);
+  else if (x_kind == 1) C1POOL(float);
+  else C1POOL(bf16_t);
+#undef C1POOL
   return 0;
 }
 
 // mask == nullptr: g is the full-resolution gradient; otherwise the
 // pooled gradient and its argmax codes.
-int geops_conv5c1_wrw(const void* x, int x_is_fp32, const bf16_t* g,
-                      const uint8_t* mask, float* part, int Nn, int H, int W,
-                      int n_wg, hipStream_t s) {
+int geops_conv5c1_wrw(const void* x, int x_kind, const bf16_t* tab,
+                      const bf16_t* g, const uint8_t* mask, float* part,
+                      int Nn, int H, int W, int n_wg, hipStream_t s) {
   if (Nn < 1 || H < 5 || W < 6 || W > C1_MAXW || (W & 1) || n_wg < 1 ||
-      (mask && (H & 1)))
+      (mask && (H & 1)) || !c1_kind_ok(x_kind, tab))
     return -1;
-#define C1WRW(TIN_, UNP_)                                                   \
-  hipLaunchKernelGGL((k_conv5c1_wrw<TIN_, UNP_>), dim3(n_wg),               \
-                     dim3(C1_THREADS), 0, s, (const TIN_*)x, g, mask, part, \
-                     Nn, H, W)
-  if (x_is_fp32) {
-    if (mask) C1WRW(float, true); else C1WRW(float, false);
-  } else {
-    if (mask) C1WRW(bf16_t, true); else C1WRW(bf16_t, false);
-  }
+#define C1WRW(TIN_)                                                         \
+  do {                                                                      \
+    if (mask)                                                               \
+      hipLaunchKernelGGL((k_conv5c1_wrw<TIN_, true>), dim3(n_wg),           \
+                         dim3(C1_THREADS), 0, s, (const TIN_*)x, g, mask,   \
+                         part, Nn, H, W, tab);                              \
+    else                                                                    \
+      hipLaunchKernelGGL((k_conv5c1_wrw<TIN_, false>), dim3(n_wg),          \
+                         dim3(C1_THREADS), 0, s, (const TIN_*)x, g, mask,   \
+                         part, Nn, H, W, tab);                              \
+  } while (0)
+  if (x_kind == 2) C1WRW(uint8_t);
+  else if (x_kind == 1) C1WRW(float);
+  else C1WRW(bf16_t);
 #undef C1WRW
   return 0;
 }

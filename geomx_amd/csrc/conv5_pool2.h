@@ -1,9 +1,10 @@
 // k_conv5_pool2_nhwc, the LDS-staged conv1 form of the fused conv + bias
 // + ReLU + max-pool stage (the block pipeline is described in conv.hip,
 // with its conv2 sibling k_conv5_pool16_nhwc). In a header because its
-// two input forms are built in two translation units: the bf16 form in
-// conv.hip, the fp32 form in conv1x32.hip, which is compiled without
-// packed fp32 instructions like the other newer kernel files.
+// three input forms are built in three translation units: the bf16 form
+// in conv.hip, the fp32 form in conv1x32.hip and the uint8 form in
+// conv1u8.hip, which are compiled without packed fp32 instructions like
+// the other newer kernel files.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,24 @@
 // image: each row once) to xb [N][Hi][Wi][4], the padded bf16 copy the
 // backward kernels read, from the registers that fed the ds_writes and
 // behind the next block's loads, like the packed results.
+//
+// TIN = uint8_t is the same form for a uint8 image [N][Hi][Wi][3] (Wi % 4
+// == 0, 4 B aligned) and a value table `tab`, bf16 [3][256]: pixel value
+// v of channel c stands for tab[c][v], which is what cf2bf gives for the
+// fp32 image x32 = table[c][x] when the host rounded the fp32 table to
+// bf16. An item is the same 4 pixels, here 12 bytes in one 3-dword load
+// (3 VGPRs in flight per item, not 12), and the conversion is 12
+// ds_read_u16 from the table, which lies behind the two row images and
+// is loaded once per workgroup ahead of the persistent loop. One lookup
+// instruction reads one channel for all 64 lanes, so which banks the
+// three channel tables start on does not matter to it. A channel's 512 B
+// are 128 dwords: lanes whose values share a dword (v >> 1) are served
+// together, lanes on different dwords of one bank serialise, so bytes
+// that vary widely across a wave cost several passes per lookup. For
+// values spread evenly the bank of a lookup is spread evenly whatever
+// offset or copy a lane reads, so replicas would not lower that; the
+// conflicts have not been counted. Everything
+// from the ds_write_b128 on, xb included, is the fp32 form's.
 template <int PIX, typename TIN = bf16_t>
 __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
     const TIN* __restrict__ in,          // [N][Hi][Wi][4], fp32: ..[3]
@@ -45,8 +64,11 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
     bf16_t* __restrict__ out,            // [N][Hop][Wop][16]
     uint8_t* __restrict__ mask,          // [N*Hop*Wop*16]
     int Nn, int Hi, int Wi, int Ho, int Wo,
-    bf16_t* __restrict__ xb) {           // fp32 form only, or nullptr
+    bf16_t* __restrict__ xb,             // fp32 / uint8 forms, or nullptr
+    const bf16_t* __restrict__ tab = nullptr) {  // uint8 form: [3][256]
   constexpr bool X32 = sizeof(TIN) == 4;
+  constexpr bool U8 = sizeof(TIN) == 1;
+  constexpr bool XIN = X32 || U8;         // stages the caller's image
   constexpr int CI = 4;
   constexpr int S = 5 * CI;             // 20
   constexpr int Sp = (S + 7) & ~7;      // 24
@@ -61,7 +83,8 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   constexpr int IMG = NROW * ARPB;
   constexpr int MAXU = Rows::MAXU;        // tiles per wave
   constexpr int NS = MAXU * nK;           // steps of the walk
-  __shared__ __attribute__((aligned(128))) char lds_rows[2 * IMG];
+  constexpr int TAB = U8 ? 3 * 512 : 0;   // the value table's bytes
+  __shared__ __attribute__((aligned(128))) char lds_rows[2 * IMG + TAB];
 
   const int lane = threadIdx.x & 63;
   const int p = lane & 15;
@@ -107,7 +130,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   }
 
   auto stage = [&](long long b, int img) {
-    if constexpr (!X32) {
+    if constexpr (!XIN) {
       const long long n = b / hblocks;
       const int ho0 = (int)(b - n * hblocks) * ROWS;
       const int nrows = (Ho - ho0) < ROWS ? (Ho - ho0) : ROWS;
@@ -117,17 +140,19 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
     }
   };
 
-  // fp32 form. Item i of a thread is 4 pixels of staged row x_ir[i],
+  // fp32 and uint8 forms. Item i of a thread is 4 pixels of staged row x_ir[i],
   // x_pix[i] pixels from the block's first one (rows are contiguous in
   // the image, so the same offset serves x and xb) and x_lds[i] bytes
   // into the row image; a row past the block's (x_ir >= staged rows,
   // always so for x_ir = NROW) is skipped.
-  constexpr int XIT = X32 ? 2 : 0;
+  constexpr int XIT = XIN ? 2 : 0;
   static_assert(NROW * (PIX / 4) <= 2 * CONV_THREADS, "2 items per thread");
+  struct U8x12 { unsigned a, b, c; };
   int x_ir[XIT + 1], x_pix[XIT + 1], x_lds[XIT + 1];
-  float4 xq[XIT + 1][3];   // the next block's pixels, as loaded
+  float4 xq[(X32 ? XIT : 0) + 1][3];   // the next block's pixels, as loaded
+  U8x12 xu[(U8 ? XIT : 0) + 1];        // the same, uint8 form
   uint4 xc[XIT + 1][2];    // the staged block's pixels, converted
-  if constexpr (X32) {
+  if constexpr (XIN) {
     const int ipr = Wi >> 2;
 #pragma unroll
     for (int i = 0; i < XIT; ++i) {
@@ -146,6 +171,20 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
                                   g * 16) = make_uint4(0u, 0u, 0u, 0u);
     }
   }
+  if constexpr (U8) {
+    // the table, once per workgroup; the barrier puts it ahead of the
+    // first block's lookups
+    for (int t = threadIdx.x; t < TAB / 4; t += CONV_THREADS)
+      reinterpret_cast<unsigned*>(lds_rows + 2 * IMG)[t] =
+          reinterpret_cast<const unsigned*>(tab)[t];
+    __syncthreads();
+  }
+  // tab[c][v] from LDS
+  auto lut = [&](int c, unsigned v) __attribute__((always_inline)) {
+    return (unsigned)*(const __attribute__((address_space(3)))
+                       unsigned short*)(uintptr_t)(lds0 + 2 * IMG + c * 512 +
+                                                   v * 2);
+  };
   // a block is (image n, first conv row ho0); the rows it stages
   auto x32_rows = [&](int ho0) {
     return ((Ho - ho0) < ROWS ? (Ho - ho0) : ROWS) + 4;
@@ -156,29 +195,53 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   // a branch are waited for where its paths join.
   auto x32_load = [&](long long n, int ho0, int nst)
                       __attribute__((always_inline)) {
-    const float* src = reinterpret_cast<const float*>(in) +
-                       (n * Hi + ho0) * (long long)Wi * 3;
+    if constexpr (U8) {
+      const uint8_t* src = reinterpret_cast<const uint8_t*>(in) +
+                           (n * Hi + ho0) * (long long)Wi * 3;
 #pragma unroll
-    for (int i = 0; i < XIT; ++i) {
-      const int pix = x_ir[i] < nst ? x_pix[i] : 0;
-      const float4* v =
-          reinterpret_cast<const float4*>(src + (long long)pix * 3);
+      for (int i = 0; i < XIT; ++i) {
+        const int pix = x_ir[i] < nst ? x_pix[i] : 0;
+        xu[i] = *reinterpret_cast<const U8x12*>(src + (long long)pix * 3);
+      }
+    } else {
+      const float* src = reinterpret_cast<const float*>(in) +
+                         (n * Hi + ho0) * (long long)Wi * 3;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) xq[i][k] = v[k];
+      for (int i = 0; i < XIT; ++i) {
+        const int pix = x_ir[i] < nst ? x_pix[i] : 0;
+        const float4* v =
+            reinterpret_cast<const float4*>(src + (long long)pix * 3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xq[i][k] = v[k];
+      }
     }
   };
   auto x32_write = [&](int nst, int img) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < XIT; ++i) {
-      const float f[12] = {xq[i][0].x, xq[i][0].y, xq[i][0].z, xq[i][0].w,
-                           xq[i][1].x, xq[i][1].y, xq[i][1].z, xq[i][1].w,
-                           xq[i][2].x, xq[i][2].y, xq[i][2].z, xq[i][2].w};
       unsigned w[8];
+      if constexpr (U8) {
+        // byte 3k + c of the item is channel c of its pixel k
+        const unsigned d[3] = {xu[i].a, xu[i].b, xu[i].c};
+        unsigned t[12];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        w[2 * k] = (unsigned)cf2bf(f[3 * k]) |
-                   ((unsigned)cf2bf(f[3 * k + 1]) << 16);
-        w[2 * k + 1] = (unsigned)cf2bf(f[3 * k + 2]);
+        for (int j = 0; j < 12; ++j)
+          t[j] = lut(j % 3, (d[j >> 2] >> ((j & 3) * 8)) & 0xFFu);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          w[2 * k] = t[3 * k] | (t[3 * k + 1] << 16);
+          w[2 * k + 1] = t[3 * k + 2];
+        }
+      } else {
+        const float f[12] = {xq[i][0].x, xq[i][0].y, xq[i][0].z, xq[i][0].w,
+                             xq[i][1].x, xq[i][1].y, xq[i][1].z, xq[i][1].w,
+                             xq[i][2].x, xq[i][2].y, xq[i][2].z, xq[i][2].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          w[2 * k] = (unsigned)cf2bf(f[3 * k]) |
+                     ((unsigned)cf2bf(f[3 * k + 1]) << 16);
+          w[2 * k + 1] = (unsigned)cf2bf(f[3 * k + 2]);
+        }
       }
       xc[i][0] = make_uint4(w[0], w[1], w[2], w[3]);
       xc[i][1] = make_uint4(w[4], w[5], w[6], w[7]);
@@ -227,10 +290,11 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   long long blk = wg;
   int img = 0;
   if (blk < n_blocks) stage(blk, 0);
-  // fp32 form: the block whose pixels xc holds, and the one in flight
+  // fp32 / uint8 forms: the block whose pixels xc holds, and the one in
+  // flight
   long long xn = 0;
   int xho0 = 0;
-  if constexpr (X32) {
+  if constexpr (XIN) {
     if (blk < n_blocks) {
       xn = blk / hblocks;
       xho0 = (int)(blk - xn * hblocks) * ROWS;
@@ -241,14 +305,14 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
   long long pn = 0;
   int phb = 0, pnpr = 0;
   for (; blk < n_blocks; blk += n_wg, img ^= 1) {
-    // (the fp32 form has no LDS-DMA in flight, and waiting here would
-    // also wait for the previous block's stores)
-    if constexpr (!X32) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // (the fp32 and uint8 forms have no LDS-DMA in flight, and waiting
+    // here would also wait for the previous block's stores)
+    if constexpr (!XIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (blk + n_wg < n_blocks) stage(blk + n_wg, img ^ 1);
     long long xn_next = 0;
     int xho0_next = 0, xnst_next = 0;
-    if constexpr (X32) {
+    if constexpr (XIN) {
       if (blk + n_wg < n_blocks) {
         xn_next = (blk + n_wg) / hblocks;
         xho0_next = (int)(blk + n_wg - xn_next * hblocks) * ROWS;
@@ -257,7 +321,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
       x32_load(xn_next, xho0_next, xnst_next);
     }
     flush(pn, phb, pnpr);
-    if constexpr (X32) x32_store(xn, xho0);
+    if constexpr (XIN) x32_store(xn, xho0);
 
     const long long n = blk / hblocks;
     const int hb = (int)(blk - n * hblocks);
@@ -311,7 +375,7 @@ __global__ __launch_bounds__(CONV_THREADS) void k_conv5_pool2_nhwc(
       pko[u] = quad_tr4(ov[0][0], ov[0][1], ov[1][0], ov[1][1], m);
       pkm[u] = pack_codes(quad_tr4(cd[0][0], cd[0][1], cd[1][0], cd[1][1], m));
     }
-    if constexpr (X32) {
+    if constexpr (XIN) {
       // the other image was last read before this block's barrier
       x32_write(xnst_next, img ^ 1);
       xn = xn_next;

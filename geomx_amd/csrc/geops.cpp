@@ -132,6 +132,10 @@ int geops_conv5_pool_x32_nhwc(const float*, const unsigned short*,
                               const float*, unsigned short*, uint8_t*,
                               unsigned short*, int, int, int, int, int, int,
                               int, hipStream_t);
+int geops_conv5_pool_u8_nhwc(const uint8_t*, const unsigned short*,
+                             const unsigned short*, const float*,
+                             unsigned short*, uint8_t*, unsigned short*, int,
+                             int, int, int, int, int, int, hipStream_t);
 void geops_pad_ch3to4_nhwc(const void*, unsigned short*, long long, int,
                            hipStream_t);
 int geops_conv5_pack_frags(const float*, long long, const long long*,
@@ -157,11 +161,12 @@ int geops_conv5_dgrad_nwg_nhwc(const unsigned short*, const uint8_t*,
                                const unsigned short*, unsigned short*, int,
                                int, int, int, int, int, int, int,
                                hipStream_t);
-int geops_conv5c1_pool(const void*, int, const unsigned short*, const float*,
-                       unsigned short*, uint8_t*, int, int, int, int,
-                       hipStream_t);
-int geops_conv5c1_wrw(const void*, int, const unsigned short*, const uint8_t*,
-                      float*, int, int, int, int, hipStream_t);
+int geops_conv5c1_pool(const void*, int, const unsigned short*,
+                       const unsigned short*, const float*, unsigned short*,
+                       uint8_t*, int, int, int, int, hipStream_t);
+int geops_conv5c1_wrw(const void*, int, const unsigned short*,
+                      const unsigned short*, const uint8_t*, float*, int, int,
+                      int, int, hipStream_t);
 int geops_fc_w_permute_bf16(const float*, unsigned short*, int, int, int,
                             hipStream_t);
 int geops_fc_w_unpermute_f32(const unsigned short*, float*, int, int, int,
@@ -761,8 +766,20 @@ void conv5_pool_nwg_nhwc(torch::Tensor in, torch::Tensor w_frags,
 // conv5_pool_nhwc gives them for pad_ch3to4_nhwc(x), which is written
 // to xb_out unless that is an empty tensor. The kernel addresses every
 // operand from the geometry alone, so all sizes are checked here.
-// n_wg == 0 is the default grid.
+// n_wg == 0 is the default grid. With `table` (the uint8 form) x holds
+// uint8 pixels and table the bf16 [3][256] values they stand for.
+static void check_value_table(const char* what, const torch::Tensor& table,
+                              int64_t channels) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kBFloat16 &&
+              table.dim() == 2 && table.size(0) == channels &&
+              table.size(1) == 256 && table.is_contiguous() &&
+              ((uintptr_t)table.data_ptr() & 3) == 0, what,
+              ": table must be a contiguous bf16 [", channels,
+              "][256] GPU tensor");
+}
+
 static void conv5_pool_x32_checked(const char* what, torch::Tensor x,
+                                   const torch::Tensor* table,
                                    torch::Tensor w_frags, torch::Tensor bias,
                                    torch::Tensor out, torch::Tensor mask,
                                    torch::Tensor xb_out, int64_t N,
@@ -770,10 +787,11 @@ static void conv5_pool_x32_checked(const char* what, torch::Tensor x,
                                    int64_t Wo, int64_t CO, int64_t n_wg) {
   TORCH_CHECK(x.is_cuda() && w_frags.is_cuda() && out.is_cuda() &&
               mask.is_cuda(), what, ": operands must be GPU tensors");
-  TORCH_CHECK(x.scalar_type() == torch::kFloat32 &&
+  TORCH_CHECK(x.scalar_type() == (table ? torch::kUInt8 : torch::kFloat32) &&
               w_frags.scalar_type() == torch::kBFloat16 &&
               out.scalar_type() == torch::kBFloat16 &&
               mask.scalar_type() == torch::kUInt8, what, ": operand dtype");
+  if (table) check_value_table(what, *table, 3);
   TORCH_CHECK(N >= 1 && N <= INT32_MAX && Ho >= 2 && Wo >= 2 &&
               Hi == Ho + 4 && Wi == Wo + 4 && Hi <= INT32_MAX && CO == 16 &&
               n_wg >= 0 && n_wg <= 65536, what, ": bad size or n_wg");
@@ -799,12 +817,22 @@ static void conv5_pool_x32_checked(const char* what, torch::Tensor x,
                 xb_out.is_non_overlapping_and_dense() &&
                 xb_out.numel() == N * Hi * Wi * 4, what,
                 ": xb_out must hold [N][Hi][Wi][4] bf16");
-  const int rc = geops_conv5_pool_x32_nhwc(
-      x.data_ptr<float>(), (const unsigned short*)w_frags.data_ptr(),
-      has_bias ? bias.data_ptr<float>() : nullptr,
-      (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(),
-      has_xb ? (unsigned short*)xb_out.data_ptr() : nullptr, (int)N, (int)Hi,
-      (int)Wi, (int)Ho, (int)Wo, (int)CO, (int)n_wg, cur_stream());
+  const float* b = has_bias ? bias.data_ptr<float>() : nullptr;
+  unsigned short* xb = has_xb ? (unsigned short*)xb_out.data_ptr() : nullptr;
+  const int rc =
+      table ? geops_conv5_pool_u8_nhwc(
+                  x.data_ptr<uint8_t>(),
+                  (const unsigned short*)table->data_ptr(),
+                  (const unsigned short*)w_frags.data_ptr(), b,
+                  (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(),
+                  xb, (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CO,
+                  (int)n_wg, cur_stream())
+            : geops_conv5_pool_x32_nhwc(
+                  x.data_ptr<float>(),
+                  (const unsigned short*)w_frags.data_ptr(), b,
+                  (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(),
+                  xb, (int)N, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)CO,
+                  (int)n_wg, cur_stream());
   TORCH_CHECK(rc == 0, what, ": unsupported geometry or alignment Hi=", Hi,
               " Wi=", Wi);
   launch_check(what);
@@ -815,8 +843,8 @@ void conv5_pool_x32_nhwc(torch::Tensor x, torch::Tensor w_frags,
                          torch::Tensor mask, torch::Tensor xb_out, int64_t N,
                          int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
                          int64_t CO) {
-  conv5_pool_x32_checked("conv5_pool_x32_nhwc", x, w_frags, bias, out, mask,
-                         xb_out, N, Hi, Wi, Ho, Wo, CO, 0);
+  conv5_pool_x32_checked("conv5_pool_x32_nhwc", x, nullptr, w_frags, bias,
+                         out, mask, xb_out, N, Hi, Wi, Ho, Wo, CO, 0);
 }
 
 // Test hook: conv5_pool_x32_nhwc on a grid of n_wg workgroups.
@@ -826,8 +854,32 @@ void conv5_pool_x32_nwg_nhwc(torch::Tensor x, torch::Tensor w_frags,
                              int64_t N, int64_t Hi, int64_t Wi, int64_t Ho,
                              int64_t Wo, int64_t CO, int64_t n_wg) {
   TORCH_CHECK(n_wg >= 1, "conv5_pool_x32_nwg_nhwc: n_wg must be positive");
-  conv5_pool_x32_checked("conv5_pool_x32_nwg_nhwc", x, w_frags, bias, out,
-                         mask, xb_out, N, Hi, Wi, Ho, Wo, CO, n_wg);
+  conv5_pool_x32_checked("conv5_pool_x32_nwg_nhwc", x, nullptr, w_frags, bias,
+                         out, mask, xb_out, N, Hi, Wi, Ho, Wo, CO, n_wg);
+}
+
+// conv1 stage from a uint8 image and its value table: x as for
+// conv5_pool_x32_nhwc but uint8, table bf16 [3][256]; out, mask and xb_out
+// are what conv5_pool_x32_nhwc gives for the fp32 image table[c][x].
+void conv5_pool_u8_nhwc(torch::Tensor x, torch::Tensor table,
+                        torch::Tensor w_frags, torch::Tensor bias,
+                        torch::Tensor out, torch::Tensor mask,
+                        torch::Tensor xb_out, int64_t N, int64_t Hi,
+                        int64_t Wi, int64_t Ho, int64_t Wo, int64_t CO) {
+  conv5_pool_x32_checked("conv5_pool_u8_nhwc", x, &table, w_frags, bias, out,
+                         mask, xb_out, N, Hi, Wi, Ho, Wo, CO, 0);
+}
+
+// Test hook: conv5_pool_u8_nhwc on a grid of n_wg workgroups.
+void conv5_pool_u8_nwg_nhwc(torch::Tensor x, torch::Tensor table,
+                            torch::Tensor w_frags, torch::Tensor bias,
+                            torch::Tensor out, torch::Tensor mask,
+                            torch::Tensor xb_out, int64_t N, int64_t Hi,
+                            int64_t Wi, int64_t Ho, int64_t Wo, int64_t CO,
+                            int64_t n_wg) {
+  TORCH_CHECK(n_wg >= 1, "conv5_pool_u8_nwg_nhwc: n_wg must be positive");
+  conv5_pool_x32_checked("conv5_pool_u8_nwg_nhwc", x, &table, w_frags, bias,
+                         out, mask, xb_out, N, Hi, Wi, Ho, Wo, CO, n_wg);
 }
 
 void conv5_wrw_nhwc(torch::Tensor in, torch::Tensor gout, torch::Tensor part,
@@ -977,19 +1029,32 @@ void conv5_dgrad_nwg_nhwc(torch::Tensor in, torch::Tensor mask,
 // ---- grayscale conv1 stage (conv1c.hip): CI = 1, CO = 16 ----
 
 // x is the [N][1][H][W] tensor as it is, fp32 or bf16 (the kernels round
-// fp32 while staging). Returns 1 for fp32, 0 for bf16.
-int check_c1_input(const torch::Tensor& x, int64_t N, int64_t H, int64_t W,
-                   const char* what) {
+// fp32 while staging), or uint8 with `table`, the bf16 [1][256] values
+// its bytes stand for (undefined or empty for the other two). Returns the
+// launchers' x_kind: 1 for fp32, 0 for bf16, 2 for uint8.
+int check_c1_input(const torch::Tensor& x, const torch::Tensor& table,
+                   int64_t N, int64_t H, int64_t W, const char* what) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), what,
               ": x must be a contiguous GPU tensor");
+  const bool has_table = table.defined() && table.numel() > 0;
   const bool f32 = x.scalar_type() == torch::kFloat32;
-  TORCH_CHECK(f32 || x.scalar_type() == torch::kBFloat16, what,
-              ": x must be fp32 or bf16");
+  const bool u8 = x.scalar_type() == torch::kUInt8;
+  if (has_table) {
+    TORCH_CHECK(u8, what, ": a table goes with a uint8 x");
+    check_value_table(what, table, 1);
+  } else {
+    TORCH_CHECK(f32 || x.scalar_type() == torch::kBFloat16, what,
+                ": x must be fp32 or bf16, or uint8 with a table");
+  }
   TORCH_CHECK(N >= 1 && H >= 5 && W >= 5 && x.numel() == N * H * W, what,
               ": x does not hold N*H*W elements");
-  TORCH_CHECK(((uintptr_t)x.data_ptr() & (f32 ? 7 : 3)) == 0, what,
+  TORCH_CHECK(((uintptr_t)x.data_ptr() & (f32 ? 7 : u8 ? 1 : 3)) == 0, what,
               ": x must be aligned to a pixel pair");
-  return f32 ? 1 : 0;
+  return u8 ? 2 : f32 ? 1 : 0;
+}
+
+const unsigned short* c1_table_ptr(const torch::Tensor& table, int kind) {
+  return kind == 2 ? (const unsigned short*)table.data_ptr() : nullptr;
 }
 
 // a dense NHWC operand: plain contiguous, or an NCHW-shaped channels_last
@@ -1019,9 +1084,11 @@ int64_t c1_grid(int64_t n_wg, int64_t blocks, int64_t cap, const char* what) {
 // resident rounds, as for the CI = 4 kernel.
 void conv5c1_pool(torch::Tensor x, torch::Tensor w_frags, torch::Tensor bias,
                   torch::Tensor out, torch::Tensor mask, int64_t N, int64_t H,
-                  int64_t W, int64_t n_wg) {
+                  int64_t W, int64_t n_wg,
+                  c10::optional<torch::Tensor> table_) {
   const char* what = "conv5c1_pool";
-  const int f32 = check_c1_input(x, N, H, W, what);
+  const torch::Tensor table = table_.value_or(torch::Tensor());
+  const int kind = check_c1_input(x, table, N, H, W, what);
   const int64_t Hop = (H - 4) / 2, Wop = (W - 4) / 2;
   check_c1_nhwc(w_frags, torch::kBFloat16, 2 * 64 * 8, what, "w_frags");
   check_c1_nhwc(out, torch::kBFloat16, N * Hop * Wop * 16, what, "out");
@@ -1036,7 +1103,8 @@ void conv5c1_pool(torch::Tensor x, torch::Tensor w_frags, torch::Tensor bias,
                 what, ": bias must be 16 fp32 values");
   const int64_t grid = c1_grid(n_wg, N * ((Hop + 1) / 2), 2048, what);
   const int rc = geops_conv5c1_pool(
-      x.data_ptr(), f32, (const unsigned short*)w_frags.data_ptr(),
+      x.data_ptr(), kind, c1_table_ptr(table, kind),
+      (const unsigned short*)w_frags.data_ptr(),
       has_bias ? bias.data_ptr<float>() : nullptr,
       (unsigned short*)out.data_ptr(), mask.data_ptr<uint8_t>(), (int)N,
       (int)H, (int)W, (int)grid, cur_stream());
@@ -1047,8 +1115,8 @@ void conv5c1_pool(torch::Tensor x, torch::Tensor w_frags, torch::Tensor bias,
 
 void c1_wrw(const char* what, torch::Tensor x, torch::Tensor g,
             const torch::Tensor* mask, torch::Tensor part, int64_t N,
-            int64_t H, int64_t W, int64_t n_wg) {
-  const int f32 = check_c1_input(x, N, H, W, what);
+            int64_t H, int64_t W, int64_t n_wg, const torch::Tensor& table) {
+  const int kind = check_c1_input(x, table, N, H, W, what);
   const int64_t Ho = H - 4, Wo = W - 4;
   if (mask) {
     check_c1_nhwc(g, torch::kBFloat16, N * (Ho / 2) * (Wo / 2) * 16, what,
@@ -1065,7 +1133,8 @@ void c1_wrw(const char* what, torch::Tensor x, torch::Tensor g,
   TORCH_CHECK(part.numel() == grid * 32 * 16, what, ": part must be [", grid,
               "][32][16]");
   const int rc = geops_conv5c1_wrw(
-      x.data_ptr(), f32, (const unsigned short*)g.data_ptr(),
+      x.data_ptr(), kind, c1_table_ptr(table, kind),
+      (const unsigned short*)g.data_ptr(),
       mask ? mask->data_ptr<uint8_t>() : nullptr, part.data_ptr<float>(),
       (int)N, (int)H, (int)W, (int)grid, cur_stream());
   TORCH_CHECK(rc == 0, what, ": unsupported geometry H=", H, " W=", W,
@@ -1077,16 +1146,19 @@ void c1_wrw(const char* what, torch::Tensor x, torch::Tensor g,
 // kh*5+kw, row 25 the bias, rows 26..31 zero) from the full-resolution
 // gradient go [N][Ho][Wo][16]; the default grid is min(768, N*ceil(Ho/2)).
 void conv5c1_wrw(torch::Tensor x, torch::Tensor go, torch::Tensor part,
-                 int64_t N, int64_t H, int64_t W, int64_t n_wg) {
-  c1_wrw("conv5c1_wrw", x, go, nullptr, part, N, H, W, n_wg);
+                 int64_t N, int64_t H, int64_t W, int64_t n_wg,
+                 c10::optional<torch::Tensor> table) {
+  c1_wrw("conv5c1_wrw", x, go, nullptr, part, N, H, W, n_wg,
+         table.value_or(torch::Tensor()));
 }
 
 // The same from the POOLED gradient gp [N][Ho/2][Wo/2][16] and its
 // argmax codes: the kernel unpools while staging.
 void conv5c1_wrw_unpool(torch::Tensor x, torch::Tensor gp, torch::Tensor mask,
                         torch::Tensor part, int64_t N, int64_t H, int64_t W,
-                        int64_t n_wg) {
-  c1_wrw("conv5c1_wrw_unpool", x, gp, &mask, part, N, H, W, n_wg);
+                        int64_t n_wg, c10::optional<torch::Tensor> table) {
+  c1_wrw("conv5c1_wrw_unpool", x, gp, &mask, part, N, H, W, n_wg,
+         table.value_or(torch::Tensor()));
 }
 
 // ---- first dense layer layout kernels (fc.hip) ----
@@ -1603,12 +1675,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv5_direct_nhwc", &conv5_direct_nhwc);
   m.def("conv5_dgrad_nwg_nhwc", &conv5_dgrad_nwg_nhwc);
   m.def("conv5_pool_nhwc", &conv5_pool_nhwc);
-  m.def("conv5c1_pool", &conv5c1_pool);
-  m.def("conv5c1_wrw", &conv5c1_wrw);
-  m.def("conv5c1_wrw_unpool", &conv5c1_wrw_unpool);
+  // (the trailing table: bf16 [1][256] with a uint8 x, else left out)
+  m.def("conv5c1_pool", &conv5c1_pool, py::arg("x"), py::arg("w_frags"),
+        py::arg("bias"), py::arg("out"), py::arg("mask"), py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("n_wg"),
+        py::arg("table") = py::none());
+  m.def("conv5c1_wrw", &conv5c1_wrw, py::arg("x"), py::arg("go"),
+        py::arg("part"), py::arg("N"), py::arg("H"), py::arg("W"),
+        py::arg("n_wg"), py::arg("table") = py::none());
+  m.def("conv5c1_wrw_unpool", &conv5c1_wrw_unpool, py::arg("x"),
+        py::arg("gp"), py::arg("mask"), py::arg("part"), py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("n_wg"),
+        py::arg("table") = py::none());
   m.def("conv5_pool_nwg_nhwc", &conv5_pool_nwg_nhwc);
   m.def("conv5_pool_x32_nhwc", &conv5_pool_x32_nhwc);
   m.def("conv5_pool_x32_nwg_nhwc", &conv5_pool_x32_nwg_nhwc);
+  m.def("conv5_pool_u8_nhwc", &conv5_pool_u8_nhwc);
+  m.def("conv5_pool_u8_nwg_nhwc", &conv5_pool_u8_nwg_nhwc);
   m.def("fc_w_permute_bf16", &fc_w_permute_bf16);
   m.def("fc_w_unpermute_f32", &fc_w_unpermute_f32);
   m.def("fc_flatten_nchw", &fc_flatten_nchw);

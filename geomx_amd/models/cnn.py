@@ -17,14 +17,15 @@ import torch.nn as nn
 
 class GeoCNN(nn.Module):
     def __init__(self, in_channels: int = 3, image_size: int = 224,
-                 num_classes: int = 10):
+                 num_classes: int = 10, input_table=None):
         super().__init__()
         from ..ops.conv import GeoConv5Pool
         from ..ops.fc import GeoFlattenLinear
         self.features = nn.Sequential(
             # both conv stages: conv+bias+relu+maxpool in ONE gfx950
             # kernel each (no full-resolution conv output in HBM)
-            GeoConv5Pool(in_channels, 16),
+            # input_table: the first stage takes uint8 images (ops/conv.py)
+            GeoConv5Pool(in_channels, 16, input_table=input_table),
             GeoConv5Pool(16, 32),
         )
         with torch.no_grad():
@@ -49,5 +50,5 @@ class GeoCNN(nn.Module):
 
 
 def geo_cnn(in_channels: int = 3, image_size: int = 224,
-            num_classes: int = 10) -> GeoCNN:
-    return GeoCNN(in_channels, image_size, num_classes)
+            num_classes: int = 10, input_table=None) -> GeoCNN:
+    return GeoCNN(in_channels, image_size, num_classes, input_table)

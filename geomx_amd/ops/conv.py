@@ -20,6 +20,12 @@ A one-channel first layer (CIr = 1, CO = 16: the grayscale conv1 stage)
 has kernels of its own (conv1c.hip): forward 'pool1' and weight gradient
 'wrw1' read the [N][1][H][W] input as it is, fp32 or bf16, with no pad,
 cast or layout kernel in front; its data gradient stays on ATen.
+A stage built with an `input_table` ([CIr][256] fp32) takes uint8 images:
+byte v of channel c stands for table[c][v] (to_tensor_table: ToTensor with
+an optional per-channel normalisation). The 'pool' forward and the
+grayscale kernels read the bytes themselves and look them up in a bf16
+copy of the table in LDS (_u8_operand); any other uint8 input is expanded
+by the gather table[c][x] and runs as the fp32 image it stands for.
 Whatever no kernel serves goes to ATen (same math, library kernels);
 one op on ATen does not move the other two off the custom kernels.
 """
@@ -182,19 +188,20 @@ def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
 
 
 def wrw1_via_kernel(x: torch.Tensor, go: torch.Tensor,
-                    mask: torch.Tensor = None):
+                    mask: torch.Tensor = None, table: torch.Tensor = None):
     """(dW [16][1][5][5], db [16]) in fp32 from k_conv5c1_wrw: x is the
-    [N][1][H][W] input, fp32 or bf16, read as it is; go the NHWC bf16
-    gradient, or with `mask` the pooled gradient and its argmax codes.
-    Slab rows 0..24 are the taps kh*5+kw, row 25 is the bias."""
+    [N][1][H][W] input, fp32 or bf16, read as it is, or uint8 with its
+    bf16 [1][256] `table`; go the NHWC bf16 gradient, or with `mask` the
+    pooled gradient and its argmax codes. Slab rows 0..24 are the taps
+    kh*5+kw, row 25 is the bias."""
     from geomx_amd import _geops
     N, _, H, W = x.shape
     n_wg = min(_WRW_NWG, N * ((H - 4 + 1) // 2))
     part = torch.empty(n_wg, 32, 16, dtype=torch.float32, device=x.device)
     if mask is not None:
-        _geops.conv5c1_wrw_unpool(x, go, mask, part, N, H, W, 0)
+        _geops.conv5c1_wrw_unpool(x, go, mask, part, N, H, W, 0, table)
     else:
-        _geops.conv5c1_wrw(x, go, part, N, H, W, 0)
+        _geops.conv5c1_wrw(x, go, part, N, H, W, 0, table)
     full = part.sum(dim=0)
     return full[:25].T.reshape(16, 1, 5, 5), full[25]
 
@@ -340,6 +347,53 @@ def _x32_operand(x: torch.Tensor, plan: Conv5Plan):
     return xc if xc.data_ptr() % 16 == 0 else None
 
 
+def to_tensor_table(channels: int, mean=None, std=None) -> torch.Tensor:
+    """The [channels][256] fp32 table of ToTensor, v -> v / 255, followed
+    where `mean` / `std` (one value per channel) are given by the
+    normalisation (v / 255 - mean[c]) / std[c]."""
+    t = (torch.arange(256, dtype=torch.float32) / 255).repeat(channels, 1)
+    if mean is not None:
+        t = t - torch.as_tensor(mean, dtype=torch.float32).reshape(-1, 1)
+    if std is not None:
+        t = t / torch.as_tensor(std, dtype=torch.float32).reshape(-1, 1)
+    return t.contiguous()
+
+
+def table_gather(table: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The fp32 image a uint8 image [N][C][H][W] stands for under a
+    [C][256] table: out[n][c][h][w] = table[c][x[n][c][h][w]], in x's
+    memory format. This is the definition of a stage with an
+    input_table; the kernels that read the bytes give its bits."""
+    C = x.shape[1]
+    idx = x.long() + 256 * torch.arange(C, device=x.device).view(1, C, 1, 1)
+    out = torch.take(table.to(x.device).float().contiguous(), idx)
+    if not x.is_contiguous() and \
+            x.is_contiguous(memory_format=torch.channels_last):
+        out = out.contiguous(memory_format=torch.channels_last)
+    return out
+
+
+def _u8_operand(x: torch.Tensor, plan: Conv5Plan):
+    """A uint8 image as the table kernels read it, or None where they do
+    not serve it, from facts about the tensor alone. 3 channels: fwd
+    'pool' on a CUDA tensor dense in channels_last whose rows are whole
+    12-byte items (Wi % 4 == 0) on a 4 B aligned base and fit the
+    232-pixel row image (conv5_pool_u8_nhwc). 1 channel: the 'wrw1'
+    plan's widths on a contiguous CUDA tensor with a 2 B aligned base
+    (conv5c1_*). Everything else is expanded by table_gather."""
+    if not (x.is_cuda and x.dtype == torch.uint8 and x.dim() == 4):
+        return None
+    if x.shape[1] == 1 and plan.wrw == "wrw1":
+        ok = x.is_contiguous() and x.data_ptr() % 2 == 0
+    else:
+        ok = (plan.fwd == "pool" and x.shape[1] == 3
+              and x.is_contiguous(memory_format=torch.channels_last)
+              and x.shape[3] % 4 == 0
+              and _ceil(x.shape[3] - 4, 16) + 4 <= 232
+              and x.data_ptr() % 4 == 0)
+    return x.detach() if ok else None
+
+
 def _w_frags(weight: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """Regather the OIHW weight into per-lane MFMA B-fragment order."""
     wb = weight.detach().to(torch.bfloat16).reshape(-1)
@@ -437,11 +491,13 @@ def _dgrad(route, go, x_real, weight, idx, mask=None, w_frags=None):
     return gx[:, :CIr] if COp != CIr else gx
 
 
-def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None):
+def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None,
+         table=None):
     """(grad_w, grad_b) in the weight's dtype; grad_b None without bias.
     With `mask` (custom routes only) `go` is the pooled gradient."""
     if route == "wrw1":
-        gw, gb = wrw1_via_kernel(xb, go, mask)   # xb: the caller's tensor
+        # xb: the caller's tensor (uint8 with its table)
+        gw, gb = wrw1_via_kernel(xb, go, mask, table)
     elif route == "aten":
         assert mask is None
         _, gw, gb = torch.ops.aten.convolution_backward(
@@ -457,10 +513,11 @@ def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None):
 
 def _out_dtype(x: torch.Tensor) -> torch.dtype:
     # outside autocast (fp32 graphs) the downstream layers expect the
-    # input dtype back; under autocast bf16 IS the compute dtype
+    # input dtype back; under autocast bf16 IS the compute dtype. A uint8
+    # image only comes here with its table: it stands for an fp32 image
     if x.dtype == torch.bfloat16 or torch.is_autocast_enabled():
         return torch.bfloat16
-    return x.dtype
+    return torch.float32 if x.dtype == torch.uint8 else x.dtype
 
 
 class _Conv5Fn(torch.autograd.Function):
@@ -474,15 +531,21 @@ class _Conv5Fn(torch.autograd.Function):
     With `pooled`, fwd='aten' returns the conv in fp32: the fused kernel
     argmaxes its fp32 accumulators, and the eager ReLU + max-pool that
     replaces it must pick the same pixels, not those that win after
-    rounding to bf16 (ties there would route gradient elsewhere)."""
+    rounding to bf16 (ties there would route gradient elsewhere).
+    `table` (bf16 [CIr][256]) comes with a uint8 x that _u8_operand
+    serves: the kernels that would read the fp32 image read the bytes
+    and the table instead, and give the same bits."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, plan, idx, pooled, x32_input=True):
+    def forward(ctx, x, weight, bias, plan, idx, pooled, x32_input=True,
+                table=None):
         N, CIr, Hi, Wi = x.shape
         CO = weight.shape[0]
         Ho, Wo = Hi - 4, Wi - 4
         c1 = "pool1" == plan.fwd or "wrw1" == plan.wrw
         x32 = _x32_operand(x, plan) if x32_input else None
+        if table is not None and not c1:
+            x32 = x   # the 3-channel uint8 image takes the fp32 image's place
         if x32 is not None:
             # the forward kernel reads the fp32 image and writes xb, the
             # bits of _nhwc_bf16(x), for the weight gradient (the only
@@ -495,8 +558,8 @@ class _Conv5Fn(torch.autograd.Function):
         elif c1:
             # the one-channel kernels read the caller's tensor (they round
             # fp32 while staging); it is what backward saves
-            xb = x if x.dtype in (torch.float32, torch.bfloat16) \
-                else x.to(torch.bfloat16)
+            xb = x if (x.dtype in (torch.float32, torch.bfloat16)
+                       or table is not None) else x.to(torch.bfloat16)
             xb = xb.detach().contiguous()
         elif plan.fwd == "aten" and plan.wrw == "aten":
             xb = x.to(torch.bfloat16)
@@ -504,7 +567,11 @@ class _Conv5Fn(torch.autograd.Function):
             xb = _nhwc_bf16(x)
         mask = w_dfrags = None
         if plan.fwd == "aten":
-            args = [xb.to(torch.bfloat16) if c1 else xb[:, :CIr],
+            if table is not None:   # c1, uint8: the bf16 image it stands for
+                xa = torch.take(table, xb.long())
+            else:
+                xa = xb.to(torch.bfloat16) if c1 else xb[:, :CIr]
+            args = [xa,
                     weight.detach().to(torch.bfloat16),
                     None if bias is None else bias.detach().to(torch.bfloat16)]
             if pooled:
@@ -526,12 +593,18 @@ class _Conv5Fn(torch.autograd.Function):
                 out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
                 mask = torch.empty(out.numel(), dtype=torch.uint8,
                                    device=x.device)
-                _geops.conv5c1_pool(xb, w_frags, b, out, mask, N, Hi, Wi, 0)
+                _geops.conv5c1_pool(xb, w_frags, b, out, mask, N, Hi, Wi, 0,
+                                    table)
             elif plan.fwd == "pool":
                 out = _empty_nhwc(N, CO, Ho // 2, Wo // 2, x.device)
                 mask = torch.empty(out.numel(), dtype=torch.uint8,
                                    device=x.device)
-                if x32 is not None:
+                if table is not None:
+                    _geops.conv5_pool_u8_nhwc(
+                        x32, table, w_frags, b, out, mask,
+                        torch.Tensor() if xb is None else xb, N, Hi, Wi, Ho,
+                        Wo, CO)
+                elif x32 is not None:
                     _geops.conv5_pool_x32_nhwc(
                         x32, w_frags, b, out, mask,
                         torch.Tensor() if xb is None else xb, N, Hi, Wi, Ho,
@@ -550,6 +623,7 @@ class _Conv5Fn(torch.autograd.Function):
         # dgrad fragments against an in-place change before backward
         ctx.save_for_backward(xb, weight, mask)
         ctx.w_dfrags = w_dfrags
+        ctx.table = table   # a constant of the stage: no gradient, no version
         ctx.plan, ctx.idx = plan, idx
         ctx.has_bias = bias is not None
         ctx.CIr = CIr
@@ -581,7 +655,7 @@ class _Conv5Fn(torch.autograd.Function):
 
         def wrw(g, m):
             return _wrw(plan.wrw, g, xb, x_real, weight, idx, ctx.has_bias,
-                        m)
+                        m, ctx.table)
 
         if mask is not None:
             # fused-pool stage: `go` is the pooled gradient. The wrw and
@@ -603,7 +677,7 @@ class _Conv5Fn(torch.autograd.Function):
             grad_x = dgrad(go, None) if need_x else None
             grad_wb = wrw(go, None) if need_w else None
         grad_w, grad_b = grad_wb if grad_wb is not None else (None, None)
-        return grad_x, grad_w, grad_b, None, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None, None
 
 
 class GeoConv5(torch.nn.Conv2d):
@@ -611,12 +685,27 @@ class GeoConv5(torch.nn.Conv2d):
     gradient and weight gradient each run on a gfx950 kernel where one
     serves the geometry (plan_conv5) and on ATen elsewhere.
     `enabled_shapes` selects the (CI, CO) whose forward takes the direct
-    kernel; routes are fixed per input shape at first use."""
+    kernel; routes are fixed per input shape at first use.
+    `input_table`, a finite fp32 [in_channels][256] tensor (see
+    to_tensor_table), makes the stage take uint8 images: it computes what
+    it computes for the fp32 image table[c][x] (table_gather), bit for
+    bit, and the input gets no gradient. Without a table, or for an input
+    of another dtype, nothing changes."""
 
     _POOLED = False
 
-    def __init__(self, in_channels, out_channels, enabled_shapes=None, **kw):
+    def __init__(self, in_channels, out_channels, enabled_shapes=None,
+                 input_table=None, **kw):
         super().__init__(in_channels, out_channels, kernel_size=5, **kw)
+        if input_table is not None:
+            input_table = torch.as_tensor(input_table, dtype=torch.float32)
+            if tuple(input_table.shape) != (in_channels, 256) or \
+                    not torch.isfinite(input_table).all():
+                raise ValueError("input_table must be a finite [%d][256] "
+                                 "tensor" % in_channels)
+            input_table = input_table.detach().clone().contiguous()
+        self.register_buffer("input_table", input_table, persistent=False)
+        self._table_bf16 = None   # (key, the kernels' copy)
         self.enabled_shapes = (DEFAULT_ENABLED if enabled_shapes is None
                                else enabled_shapes)
         # False keeps an fp32 3-channel image on the pad kernel in front
@@ -639,14 +728,36 @@ class GeoConv5(torch.nn.Conv2d):
             ent = self._routes[key] = (plan, idx)
         return ent
 
-    def _conv(self, x, plan, idx):
+    def _input(self, x, plan):
+        """(x, table): a uint8 image of a stage with a table either stays
+        as it is, with the bf16 copy of the table its kernels look it up
+        in, or becomes the fp32 image it stands for. The copy is rounded
+        to nearest even as cf2bf rounds (the table is finite), once per
+        table tensor."""
+        t = self.input_table
+        if t is None or x.dtype != torch.uint8 or x.dim() != 4:
+            return x, None
+        if plan == _ALL_ATEN or _u8_operand(x, plan) is None:
+            return table_gather(t, x), None
+        # (the cache holds the table tensor itself: a new buffer, an
+        # in-place change or another device make a new copy)
+        c = self._table_bf16
+        if c is None or c[0] is not t or c[1:3] != (t._version, x.device):
+            c = self._table_bf16 = (t, t._version, x.device,
+                                    t.to(x.device, torch.bfloat16)
+                                    .contiguous())
+        return x.detach(), c[3]
+
+    def _conv(self, x, plan, idx, table=None):
         if plan == _ALL_ATEN:
             return torch.nn.Conv2d.forward(self, x)
         return _Conv5Fn.apply(x, self.weight, self.bias, plan, idx,
-                              self._POOLED, self.x32_input)
+                              self._POOLED, self.x32_input, table)
 
     def forward(self, x):
-        return self._conv(x, *self._route(x))
+        plan, idx = self._route(x)
+        x, table = self._input(x, plan)
+        return self._conv(x, plan, idx, table)
 
 
 class GeoConv5Pool(GeoConv5):
@@ -660,7 +771,8 @@ class GeoConv5Pool(GeoConv5):
 
     def forward(self, x):
         plan, idx = self._route(x)
-        y = self._conv(x, plan, idx)
+        x, table = self._input(x, plan)
+        y = self._conv(x, plan, idx, table)
         if plan.fwd in ("pool", "pool1"):
             return y
         y = F.max_pool2d(F.relu(y), 2, 2)

@@ -14,7 +14,11 @@ only, so the same script times both sides of an A/B.
 Where the build has conv5_pool_x32_nhwc, the conv1 input path is timed
 both ways in the same run (the machines of the pool differ by ~5 %): the
 3 -> 4 channel pad kernel plus the bf16 forward, against the forward that
-reads the fp32 image itself, with and without its padded side output."""
+reads the fp32 image itself, with and without its padded side output.
+
+Where the build has conv5_pool_u8_nhwc, the uint8 form is timed in that
+run too, with and without the side output, next to the standalone
+x.float() / 255 pass it replaces in front of the fp32 form."""
 import argparse
 import os
 import statistics
@@ -32,7 +36,7 @@ ITERS = 50
 SHAPES = [("conv1 fwd", 3, 16, 224), ("conv2 fwd", 16, 32, 110)]
 
 
-def bench(f, reps):
+def bench(f, reps, spread=False):
     ts = []
     for _ in range(reps):
         for _ in range(5):
@@ -46,6 +50,8 @@ def bench(f, reps):
         end.record()
         torch.cuda.synchronize()
         ts.append(beg.elapsed_time(end) / ITERS)
+    if spread:
+        return min(ts), statistics.median(ts), max(ts)
     return min(ts), statistics.median(ts)
 
 
@@ -83,6 +89,60 @@ def x32_ab(reps):
         _geops.conv5_pool_x32_nhwc(x, w_frags, b, outs[1], masks[1],
                                    torch.Tensor(), *dims, 16)
 
+    runs = [("pad kernel alone", pad), ("bf16 forward alone", fwd),
+            ("pad + bf16 forward", parent), ("fp32 forward + copy", fused),
+            ("fp32 forward, no copy", fused_no_copy),
+            ("pad + bf16 forward", parent), ("fp32 forward + copy", fused)]
+    if getattr(_geops, "conv5_pool_u8_nhwc", None) is not None:
+        table = C.to_tensor_table(3, [0.485, 0.456, 0.406],
+                                  [0.229, 0.224, 0.225]).to(DEV)
+        tab = table.to(torch.bfloat16)
+        xu = torch.randint(0, 256, (N, h, h, 3), device=DEV,
+                           dtype=torch.uint8).permute(0, 3, 1, 2)
+        x32 = C.table_gather(table, xu)
+        out_u, mask_u = torch.empty_like(outs[0]), torch.empty_like(masks[0])
+        xb_u = C._empty_nhwc(N, 4, h, h, DEV)
+
+        def expand():    # the pass a uint8 dataset needs ahead of the fp32 form
+            return xu.float() / 255
+
+        def x32_copy():
+            _geops.conv5_pool_x32_nhwc(x32, w_frags, b, outs[1], masks[1],
+                                       xbs[1], *dims, 16)
+
+        def x32_no_copy():
+            _geops.conv5_pool_x32_nhwc(x32, w_frags, b, outs[1], masks[1],
+                                       torch.Tensor(), *dims, 16)
+
+        def u8_copy():
+            _geops.conv5_pool_u8_nhwc(xu, tab, w_frags, b, out_u, mask_u,
+                                      xb_u, *dims, 16)
+
+        def u8_no_copy():
+            _geops.conv5_pool_u8_nhwc(xu, tab, w_frags, b, out_u, mask_u,
+                                      torch.Tensor(), *dims, 16)
+
+        def expand_x32():
+            expand()
+            x32_copy()
+
+        x32_copy()
+        u8_copy()
+        same_u = torch.equal(out_u.view(torch.int16),
+                             outs[1].view(torch.int16)) and \
+            torch.equal(mask_u, masks[1]) and \
+            torch.equal(xb_u.view(torch.int16), xbs[1].view(torch.int16))
+        print(f"conv1 uint8 form: out, mask, xb equal to the fp32 form on "
+              f"table[c][x]: {same_u}")
+        runs += [("uint8 -> fp32 pass alone", expand),
+                 ("fp32 forward + copy (img)", x32_copy),
+                 ("fp32 forward, no copy (img)", x32_no_copy),
+                 ("uint8 forward + copy", u8_copy),
+                 ("uint8 forward, no copy", u8_no_copy),
+                 ("pass + fp32 forward + copy", expand_x32),
+                 ("uint8 forward + copy", u8_copy),
+                 ("bf16 forward alone", fwd)]
+
     parent()
     fused()
     same = all(torch.equal(a.view(torch.int16), c.view(torch.int16))
@@ -91,14 +151,10 @@ def x32_ab(reps):
         torch.equal(masks[0], masks[1])
     print(f"conv1 input path: fused out, mask, xb equal to pad + forward: "
           f"{same}")
-    for name, f in (("pad kernel alone", pad), ("bf16 forward alone", fwd),
-                    ("pad + bf16 forward", parent),
-                    ("fp32 forward + copy", fused),
-                    ("fp32 forward, no copy", fused_no_copy),
-                    ("pad + bf16 forward", parent),
-                    ("fp32 forward + copy", fused)):
-        lo, med = bench(f, reps)
-        print(f"conv1 {name:24s} min {lo:7.4f}  median {med:7.4f} ms")
+    for name, f in runs:
+        lo, med, hi = bench(f, reps, spread=True)
+        print(f"conv1 {name:28s} min {lo:7.4f}  median {med:7.4f}  "
+              f"max {hi:7.4f} ms")
 
 
 def main():

@@ -45,7 +45,8 @@ ext = CUDAExtension(
 # one rounded multiply and two rounded additions (bsc_mom.h) and is too.
 # conv1x32.hip (the conv1 stage from the fp32 image) is too: its kernel is
 # the fp32 instantiation of the template in conv5_pool2.h, whose bf16
-# instantiation conv.hip keeps building as before. lars.hip (layer-wise LARS)
+# instantiation conv.hip keeps building as before; conv1u8.hip is the uint8
+# instantiation of the same template, built like its fp32 sibling. lars.hip (layer-wise LARS)
 # specifies its sums of squares one rounded operation at a time and is too.
 # The extension's flag list is one for all of its sources, so these are
 # compiled here, with the same flags plus the feature switch, and linked
@@ -56,6 +57,7 @@ NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
                      "geomx_amd/csrc/conv1c.hip",
                      "geomx_amd/csrc/bscselect.hip",
                      "geomx_amd/csrc/conv1x32.hip",
+                     "geomx_amd/csrc/conv1u8.hip",
                      "geomx_amd/csrc/lars.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h",
                      "geomx_amd/csrc/bsc_mom.h",
