@@ -177,6 +177,11 @@ int geops_fc_w_pack2_bf16(const float*, unsigned short*, unsigned short*,
                           int, int, int, hipStream_t);
 int geops_fc_w_unpermute_into(const unsigned short*, float*, int, int, int,
                               hipStream_t);
+int geops_conv5_wrw_finalize(const float*, const long long*, float*, float*,
+                             int, int, int, long long, long long, long long,
+                             long long, hipStream_t);
+int geops_many(int, int, const void* const*, void* const*, const long long*,
+               hipStream_t);
 void geops_tr16_probe(const unsigned short*, unsigned short*, hipStream_t);
 void geops_tr16_probe2(const unsigned short*, const int*, unsigned short*,
                        hipStream_t);
@@ -1297,6 +1302,122 @@ torch::Tensor fc_flatten_nchw(torch::Tensor x, int64_t N, int64_t C,
   return y;
 }
 
+// The summed wrw slab `full` fp32 [T16][CO] -> the gradients of a conv
+// weight [CO][CIr][5][5] and its bias [CO], written as x + 0.0f into
+// caller-given fp32 destinations (finalize.hip): dw with the weight's
+// shape and any dense strides (OIHW or channels_last), db contiguous;
+// either may be None. idx is the int64 unpack table of the weight shape.
+void conv5_wrw_finalize(torch::Tensor full, torch::Tensor idx,
+                        c10::optional<torch::Tensor> dw,
+                        c10::optional<torch::Tensor> db, int64_t CO,
+                        int64_t CIr, int64_t T16) {
+  TORCH_CHECK(full.is_cuda() && full.is_contiguous() &&
+                  full.scalar_type() == torch::kFloat32 &&
+                  full.numel() == T16 * CO,
+              "full must be a contiguous GPU fp32 tensor of ", T16 * CO,
+              " elements");
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
+                  idx.scalar_type() == torch::kInt64 &&
+                  idx.numel() == CO * CIr * 25,
+              "idx must be a contiguous GPU int64 tensor of ", CO * CIr * 25,
+              " elements");
+  TORCH_CHECK(idx.device() == full.device(), "idx must be on full's device");
+  check_on_current_device(full, "full");
+  TORCH_CHECK(dw.has_value() || db.has_value(), "no destination given");
+  float *pw = nullptr, *pb = nullptr;
+  long long st[4] = {0, 0, 0, 0};
+  if (dw.has_value()) {
+    const auto& t = *dw;
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                    t.dim() == 4 && t.size(0) == CO && t.size(1) == CIr &&
+                    t.size(2) == 5 && t.size(3) == 5 &&
+                    t.is_non_overlapping_and_dense(),
+                "dw must be a dense GPU fp32 tensor of shape [", CO, "][",
+                CIr, "][5][5]");
+    TORCH_CHECK(t.device() == full.device(), "dw must be on full's device");
+    for (int d = 0; d < 4; ++d) st[d] = t.stride(d);
+    pw = t.data_ptr<float>();
+  }
+  if (db.has_value()) {
+    const auto& t = *db;
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                    t.is_contiguous() && t.numel() == CO,
+                "db must be a contiguous GPU fp32 tensor of ", CO,
+                " elements");
+    TORCH_CHECK(t.device() == full.device(), "db must be on full's device");
+    pb = t.data_ptr<float>();
+  }
+  const int rc = geops_conv5_wrw_finalize(
+      full.data_ptr<float>(), (const long long*)idx.data_ptr<int64_t>(), pw,
+      pb, (int)CO, (int)CIr, (int)T16, st[0], st[1], st[2], st[3],
+      cur_stream());
+  TORCH_CHECK(rc == 0, "conv5_wrw_finalize: unsupported geometry CO=", CO,
+              " CIr=", CIr, " T16=", T16);
+  launch_check("conv5_wrw_finalize");
+}
+
+// One launch over up to 8 (src, dst) pairs of contiguous GPU tensors of
+// equal length on the current device (finalize.hip). kind 0: fp32 -> bf16,
+// kind 1: bf16 -> fp32 stored as x + 0.0f, kind 2: dst fp32 cleared.
+static void many_launch(int kind, const char* what,
+                        const std::vector<torch::Tensor>& src,
+                        const std::vector<torch::Tensor>& dst) {
+  const auto sdt = kind == 0 ? torch::kFloat32 : torch::kBFloat16;
+  const auto ddt = kind == 0 ? torch::kBFloat16 : torch::kFloat32;
+  TORCH_CHECK(!dst.empty() && dst.size() <= 8, what,
+              ": 1 to 8 tensors per launch, got ", dst.size());
+  TORCH_CHECK(kind == 2 || src.size() == dst.size(), what,
+              ": as many sources as destinations");
+  const void* ps[8];
+  void* pd[8];
+  long long n[8];
+  for (size_t k = 0; k < dst.size(); ++k) {
+    const auto& d = dst[k];
+    TORCH_CHECK(d.is_cuda() && d.is_contiguous() && d.scalar_type() == ddt,
+                what, ": destination ", k, " must be a contiguous GPU ",
+                ddt, " tensor");
+    check_on_current_device(d, "destination");
+    pd[k] = d.data_ptr();
+    n[k] = d.numel();
+    ps[k] = nullptr;
+    if (kind != 2) {
+      const auto& s = src[k];
+      TORCH_CHECK(s.is_cuda() && s.is_contiguous() &&
+                      s.scalar_type() == sdt && s.numel() == d.numel() &&
+                      s.device() == d.device(),
+                  what, ": source ", k, " must be a contiguous GPU ", sdt,
+                  " tensor of its destination's length and device");
+      ps[k] = s.data_ptr();
+    }
+  }
+  const int rc = geops_many(kind, (int)dst.size(), ps, pd, n, cur_stream());
+  TORCH_CHECK(rc == 0, what, ": nothing to do (every tensor is empty)");
+  launch_check(what);
+}
+
+// The bf16 copies of up to 8 fp32 tensors (the bits of t.to(bfloat16)),
+// each a fresh tensor of its source's shape, from one launch.
+std::vector<torch::Tensor> cast_many_f32_bf16(
+    std::vector<torch::Tensor> src) {
+  std::vector<torch::Tensor> dst;
+  for (const auto& s : src)
+    dst.push_back(torch::empty(s.sizes(),
+                               s.options().dtype(torch::kBFloat16)));
+  many_launch(0, "cast_many_f32_bf16", src, dst);
+  return dst;
+}
+
+// bf16 tensors -> caller-given fp32 destinations, stored as x + 0.0f:
+// the bytes `zeros + src.float()` has.
+void cast_many_bf16_f32_into(std::vector<torch::Tensor> src,
+                             std::vector<torch::Tensor> dst) {
+  many_launch(1, "cast_many_bf16_f32_into", src, dst);
+}
+
+void zero_many_f32(std::vector<torch::Tensor> dst) {
+  many_launch(2, "zero_many_f32", {}, dst);
+}
+
 void pad_ch3to4_nhwc(torch::Tensor in, torch::Tensor out, int64_t npix) {
   TORCH_CHECK(in.is_cuda() && out.is_cuda());
   TORCH_CHECK(out.scalar_type() == torch::kBFloat16);
@@ -1699,6 +1820,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("C"), py::arg("HW"), py::arg("want_perm"),
         py::arg("wb_out") = py::none(), py::arg("wp_out") = py::none());
   m.def("fc_w_unpermute_into", &fc_w_unpermute_into);
+  m.def("conv5_wrw_finalize", &conv5_wrw_finalize);
+  m.def("cast_many_f32_bf16", &cast_many_f32_bf16);
+  m.def("cast_many_bf16_f32_into", &cast_many_bf16_f32_into);
+  m.def("zero_many_f32", &zero_many_f32);
   m.def("tr16_probe2", [](torch::Tensor in, torch::Tensor addr,
                           torch::Tensor out) {
     TORCH_CHECK(in.is_cuda() && addr.is_cuda() && out.is_cuda());

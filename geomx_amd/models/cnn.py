@@ -45,8 +45,22 @@ class GeoCNN(nn.Module):
             nn.Linear(128, num_classes),
         )
 
+    def grad_sink_parameters(self):
+        """The tail's parameters (classifier.3 and .5): the fused tail's
+        backward writes their gradients in place (gradsink.py)."""
+        c = self.classifier
+        return (c[3].weight, c[3].bias, c[5].weight, c[5].bias)
+
     def forward(self, x):
-        return self.classifier(self.features(x))
+        from ..ops.fc import mlp_tail, tail_route
+        c = self.classifier
+        y = c[1](c[0](self.features(x)))
+        # ReLU, fc2, ReLU, fc3 as one autograd Function on the modules'
+        # own parameters where it serves the tensors; the modules
+        # themselves otherwise
+        if tail_route(y, c[3], c[5]):
+            return mlp_tail(y, c[3], c[5])
+        return c[5](c[4](c[3](c[2](y))))
 
 
 def geo_cnn(in_channels: int = 3, image_size: int = 224,

@@ -61,6 +61,19 @@ def _flat_inplace(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.view(-1)
 
 
+def zero_many_f32(ranges) -> None:
+    """Clear contiguous fp32 tensors: on the GPU one launch of
+    k_zero_many_f32 per 8 of them (finalize.hip), on the CPU zero_()."""
+    ranges = [r for r in ranges if r.numel()]
+    if not _on_gpu(*ranges):
+        for r in ranges:
+            r.zero_()
+        return
+    lib = _require_native()
+    for i in range(0, len(ranges), 8):
+        lib.zero_many_f32(ranges[i:i + 8])
+
+
 # ---------------------------------------------------------------------------
 # 2bit
 # ---------------------------------------------------------------------------

@@ -37,6 +37,7 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
+from .. import gradsink
 from . import native_available
 
 _SUPPORTED_FWD = {(4, 16), (16, 32), (16, 16), (32, 32)}
@@ -156,14 +157,13 @@ def build_wrw_unpack_index(weight_shape):
     return (slot * CO + o).reshape(-1), (tiles + 1) * 16
 
 
-def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
-                   unpack_idx: torch.Tensor, T16: int, weight_shape,
-                   want_bias: bool = False, mask: torch.Tensor = None):
-    """Run the custom wrw kernel; returns dW in OIHW fp32 (and, with
-    want_bias, the bias gradient the kernel fused via its all-ones tap
-    tile — slab row T16-16). With `mask`, `go` is the max-POOLED
-    gradient and mask its argmax codes: the kernel unpools while
-    staging (same slabs, same sums, bit-identical result)."""
+def _wrw_slab_sum(xb_padded: torch.Tensor, go: torch.Tensor, T16: int,
+                  mask: torch.Tensor = None) -> torch.Tensor:
+    """The wrw4 / wrw16 kernel's partial slabs summed over the
+    workgroups: fp32 [T16][CO], tap rows in the kernel's slot order and
+    the fused bias in row T16-16. With `mask`, `go` is the max-POOLED
+    gradient and mask its argmax codes: the kernel unpools while staging
+    (same slabs, same sums, bit-identical result)."""
     from geomx_amd import _geops
     N, CI, Hi, Wi = xb_padded.shape
     CO = go.shape[1]
@@ -180,11 +180,52 @@ def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
     else:
         _geops.conv5_wrw_nhwc(xb_padded, go, part, N, Hi, Wi, Ho, Wo, CI,
                               CO, n_wg)
-    full = part.sum(dim=0)
+    return part.sum(dim=0)
+
+
+def wrw_via_kernel(xb_padded: torch.Tensor, go: torch.Tensor,
+                   unpack_idx: torch.Tensor, T16: int, weight_shape,
+                   want_bias: bool = False, mask: torch.Tensor = None):
+    """Run the custom wrw kernel; returns dW in OIHW fp32 (and, with
+    want_bias, the bias gradient the kernel fused via its all-ones tap
+    tile — slab row T16-16). `mask` as in _wrw_slab_sum."""
+    full = _wrw_slab_sum(xb_padded, go, T16, mask)
     dw = full.reshape(-1)[unpack_idx].reshape(weight_shape)
     if want_bias:
         return dw, full[T16 - 16]
     return dw
+
+
+def wrw_into_sinks(xb_padded: torch.Tensor, go: torch.Tensor,
+                   unpack_idx: torch.Tensor, T16: int, weight: torch.Tensor,
+                   w_sink, b_sink, want_bias: bool,
+                   mask: torch.Tensor = None):
+    """The wrw4 / wrw16 gradients written where the trainer consumes
+    them (gradsink.py): the same slabs and the same ATen sum over them as
+    wrw_via_kernel, then ONE launch of k_conv5_wrw_finalize in place of
+    the gather, the reshape and autograd's two `0 + x` accumulations. It
+    writes the weight gradient into the weight's span (the parameter's
+    own strides, OIHW or channels_last) and the bias gradient into the
+    bias's span, or into a fresh tensor where the bias has no armed
+    sink. Returns (grad_w, grad_b), or None where the weight's sink
+    hands out no span (none attached, or spent): the caller then runs
+    wrw_via_kernel."""
+    if w_sink is None or weight.dtype != torch.float32:
+        return None
+    gw = w_sink.take()
+    if gw is None:
+        return None
+    from geomx_amd import _geops
+    gb = None
+    if want_bias:
+        gb = None if b_sink is None else b_sink.take()
+        if gb is None:
+            gb = torch.empty(weight.shape[0], dtype=torch.float32,
+                             device=go.device)
+    full = _wrw_slab_sum(xb_padded, go, T16, mask)
+    _geops.conv5_wrw_finalize(full, unpack_idx, gw, gb, weight.shape[0],
+                              weight.shape[1], T16)
+    return gw, gb
 
 
 def wrw1_via_kernel(x: torch.Tensor, go: torch.Tensor,
@@ -492,9 +533,17 @@ def _dgrad(route, go, x_real, weight, idx, mask=None, w_frags=None):
 
 
 def _wrw(route, go, xb, x_real, weight, idx, has_bias, mask=None,
-         table=None):
+         table=None, sinks=(None, None)):
     """(grad_w, grad_b) in the weight's dtype; grad_b None without bias.
-    With `mask` (custom routes only) `go` is the pooled gradient."""
+    With `mask` (custom routes only) `go` is the pooled gradient.
+    `sinks`: the gradient sinks of weight and bias the forward recorded;
+    on the wrw4 / wrw16 routes an armed weight sink gets the gradients
+    written into the spans (wrw_into_sinks)."""
+    if route in ("wrw4", "wrw16"):
+        done = wrw_into_sinks(xb, go, idx.wrw, idx.t16, weight, sinks[0],
+                              sinks[1], has_bias, mask)
+        if done is not None:
+            return done
     if route == "wrw1":
         # xb: the caller's tensor (uint8 with its table)
         gw, gb = wrw1_via_kernel(xb, go, mask, table)
@@ -626,6 +675,8 @@ class _Conv5Fn(torch.autograd.Function):
         ctx.table = table   # a constant of the stage: no gradient, no version
         ctx.plan, ctx.idx = plan, idx
         ctx.has_bias = bias is not None
+        ctx.sinks = (gradsink.sink_of(weight),
+                     None if bias is None else gradsink.sink_of(bias))
         ctx.CIr = CIr
         ctx.x_shape = tuple(x.shape)
         if out.dtype == torch.float32:  # the module rounds after pooling
@@ -654,8 +705,13 @@ class _Conv5Fn(torch.autograd.Function):
                           ctx.w_dfrags)
 
         def wrw(g, m):
+            # the spans are written only where autograd asked for the
+            # weight's gradient and will accumulate what is returned
+            sinks = ctx.sinks if ctx.needs_input_grad[1] else (None, None)
+            if not (ctx.has_bias and ctx.needs_input_grad[2]):
+                sinks = (sinks[0], None)
             return _wrw(plan.wrw, g, xb, x_real, weight, idx, ctx.has_bias,
-                        m, ctx.table)
+                        m, ctx.table, sinks)
 
         if mask is not None:
             # fused-pool stage: `go` is the pooled gradient. The wrw and
@@ -712,6 +768,14 @@ class GeoConv5(torch.nn.Conv2d):
         # of the forward (the route every other input takes)
         self.x32_input = True
         self._routes = {}  # (input shape, device) -> (plan, indices)
+
+    def grad_sink_parameters(self):
+        """The parameters whose gradient the backward can write in place
+        (gradsink.py): weight and bias, on the wrw4 / wrw16 routes. On
+        every other route they arrive through autograd and the trainer's
+        hook puts them into the span."""
+        return (self.weight,) if self.bias is None \
+            else (self.weight, self.bias)
 
     def _route(self, x):
         key = (x.shape, x.device)

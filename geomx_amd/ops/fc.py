@@ -98,6 +98,7 @@ class _FlattenLinearFn(torch.autograd.Function):
         ctx.save_for_backward(xf)
         ctx.wp = wp
         ctx.sink = gradsink.sink_of(weight)
+        ctx.b_sink = None if bias is None else gradsink.sink_of(bias)
         ctx.geom = (N, C, H, W, weight.shape[0])
         ctx.x_dtype = x.dtype
         ctx.b_dtype = None if bias is None else bias.dtype
@@ -125,7 +126,15 @@ class _FlattenLinearFn(torch.autograd.Function):
             else:
                 grad_w = _geops.fc_w_unpermute_f32(gp, O, C, H * W)
         if ctx.b_dtype is not None and ctx.needs_input_grad[2]:
-            grad_b = dy.sum(0).to(ctx.b_dtype)
+            gb = dy.sum(0)
+            # an fp32 bias with an armed sink: the cast writes the span
+            grad_b = None
+            if ctx.b_sink is not None and ctx.b_dtype == torch.float32:
+                grad_b = ctx.b_sink.take()
+            if grad_b is not None:
+                _geops.cast_many_bf16_f32_into([gb], [grad_b])
+            else:
+                grad_b = gb.to(ctx.b_dtype)
         return grad_x, grad_w, grad_b
 
 
@@ -135,10 +144,108 @@ class GeoFlattenLinear(torch.nn.Linear):
 
     def grad_sink_parameters(self):
         """The parameters whose gradient the backward can write in place
-        (gradsink.py): the weight."""
-        return (self.weight,)
+        (gradsink.py): weight and bias."""
+        return (self.weight,) if self.bias is None \
+            else (self.weight, self.bias)
 
     def forward(self, x):
         if native_route(x, self.weight):
             return _FlattenLinearFn.apply(x, self.weight, self.bias)
         return F.linear(torch.flatten(x, 1), self.weight, self.bias)
+
+
+# ---------------------------------------------------------------------
+# the classifier tail: ReLU -> Linear -> ReLU -> Linear
+# ---------------------------------------------------------------------
+
+def tail_route(x: torch.Tensor, fc2: torch.nn.Linear,
+               fc3: torch.nn.Linear) -> bool:
+    """True when the tail runs as one Function: a 2-D bf16 GPU
+    activation under bf16 autocast with the extension loaded, and two
+    nn.Linear with fp32 contiguous weights and biases on its device."""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16
+            and x.shape[0] > 0 and native_available()
+            and torch.is_autocast_enabled("cuda")
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+        return False
+    for m in (fc2, fc3):
+        if m.bias is None:
+            return False
+        for p in (m.weight, m.bias):
+            if not (p.dtype == torch.float32 and p.device == x.device
+                    and p.is_contiguous()):
+                return False
+    return x.shape[1] == fc2.in_features and \
+        fc2.out_features == fc3.in_features
+
+
+class _MlpTailFn(torch.autograd.Function):
+    """relu -> linear(w2, b2) -> relu -> linear(w3, b3) as eager autograd
+    under bf16 autocast computes it, kernel for kernel on the library
+    side (the same F.linear, torch.mm, sum(0) and ReLU calls on the same
+    operands), with the per-tensor casts gathered: one launch makes the
+    four bf16 operands (k_cast_many_f32_bf16), one launch writes the
+    four fp32 gradients (k_cast_many_bf16_f32_into) into the parameters'
+    gradient sinks (gradsink.py), or into fresh tensors where a
+    parameter has no armed sink. The operands are cast on every forward:
+    no copy outlives a step."""
+
+    @staticmethod
+    def forward(ctx, x, w2, b2, w3, b3):
+        from geomx_amd import _geops
+        w2b, b2b, w3b, b3b = _geops.cast_many_f32_bf16(
+            [w2.detach(), b2.detach(), w3.detach(), b3.detach()])
+        with torch.autocast("cuda", enabled=False):
+            h1 = torch.relu(x.detach())
+            h2 = torch.relu(F.linear(h1, w2b, b2b))
+            y = F.linear(h2, w3b, b3b)
+        ctx.save_for_backward(h1, h2, w2b, w3b)
+        ctx.sinks = [gradsink.sink_of(p) for p in (w2, b2, w3, b3)]
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from geomx_amd import _geops
+        h1, h2, w2b, w3b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = grad_out.to(torch.bfloat16).contiguous()
+        small = [None] * 4   # bf16 gradients of w2, b2, w3, b3
+        grad_x = None
+        if need[3]:
+            small[2] = torch.mm(dy.t(), h2)
+        if need[4]:
+            small[3] = dy.sum(0)
+        if need[0] or need[1] or need[2]:
+            g2 = torch.ops.aten.threshold_backward(torch.mm(dy, w3b), h2, 0)
+            if need[1]:
+                small[0] = torch.mm(g2.t(), h1)
+            if need[2]:
+                small[1] = g2.sum(0)
+            if need[0]:
+                grad_x = torch.ops.aten.threshold_backward(
+                    torch.mm(g2, w2b), h1, 0)
+        grads = [None] * 4
+        src, dst = [], []
+        for k, g in enumerate(small):
+            if g is None:
+                continue
+            out = None if ctx.sinks[k] is None else ctx.sinks[k].take()
+            if out is None:
+                out = torch.empty(g.shape, dtype=torch.float32,
+                                  device=g.device)
+            grads[k] = out
+            src.append(g)
+            dst.append(out)
+        if src:
+            _geops.cast_many_bf16_f32_into(src, dst)
+        return (grad_x, *grads)
+
+
+def mlp_tail(x: torch.Tensor, fc2: torch.nn.Linear,
+             fc3: torch.nn.Linear) -> torch.Tensor:
+    """fc3(relu(fc2(relu(x)))) on the parameters of the two modules:
+    _MlpTailFn where tail_route serves it, the eager chain otherwise."""
+    if tail_route(x, fc2, fc3):
+        return _MlpTailFn.apply(x, fc2.weight, fc2.bias, fc3.weight,
+                                fc3.bias)
+    return fc3(F.relu(fc2(F.relu(x))))

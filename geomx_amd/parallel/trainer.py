@@ -52,7 +52,8 @@ from ..topology import Topology
 class _Bucket:
     __slots__ = ("params", "flat", "param_flat", "views", "ready", "expected",
                  "work", "index", "bsc_u", "bsc_v", "dgt", "res2bit",
-                 "wan_buf", "wan_work", "wan_ready", "clear", "seg_off")
+                 "wan_buf", "wan_work", "wan_ready", "clear", "gaps",
+                 "seg_off")
 
     def __init__(self, index: int):
         self.index = index
@@ -63,6 +64,9 @@ class _Bucket:
         # what zero_grad() fills: the maximal contiguous ranges of
         # `flat` outside every gradient-sink span
         self.clear: List[torch.Tensor] = []
+        # ranges between sink spans that hold only alignment padding,
+        # kept only where something can write them (_pad_stays_zero)
+        self.gaps: List[torch.Tensor] = []
         # lbsgd: offsets of the parameters in the bucket (one LARS layer
         # each, its alignment padding included), else None
         self.seg_off: Optional[torch.Tensor] = None
@@ -200,7 +204,20 @@ class GeoTrainer:
                                        device=self.device)
             off = 0
             lo = 0   # start of the current run of non-sink elements
+            live = False   # the run holds an ordinary parameter
             offs = [0]
+
+            def close_run(hi):
+                # A run that holds only alignment padding is zero from
+                # allocation and stays zero where nothing writes it
+                # (_pad_stays_zero): it is left out. Where something can,
+                # it goes to `gaps`, which zero_grad() clears in one
+                # launch per bucket.
+                if hi > lo:
+                    if live:
+                        b.clear.append(b.flat[lo:hi])
+                    elif not self._pad_stays_zero():
+                        b.gaps.append(b.flat[lo:hi])
             for p in b.params:
                 n = p.numel()
                 view = _alias_view(b.flat, off, p)
@@ -217,18 +234,40 @@ class GeoTrainer:
                     sink = gradsink.GradSink(b.flat, view, p)
                     gradsink.attach(p, sink)
                     self.sinks[p] = sink
-                    if off > lo:
-                        b.clear.append(b.flat[lo:off])
+                    close_run(off)
                     lo = off + n   # the span's own padding is cleared
+                    live = False
+                else:
+                    live = True
                 off += aligned(n)
                 offs.append(off)
-            if total > lo:
-                b.clear.append(b.flat[lo:total])
+            close_run(total)
             if self.spec.name == "lbsgd":
                 # the padding is zero in param_flat, flat and the state and
                 # stays zero, so it changes no norm
                 b.seg_off = torch.tensor(offs, dtype=torch.int64,
                                          device=self.device)
+
+    def _pad_stays_zero(self) -> bool:
+        """Whether the alignment padding of a gradient bucket, zero from
+        allocation, can only ever be rewritten with zero. Autograd, the
+        sinks' kernels and _settle_grads write parameter spans alone.
+        Everything else that writes `flat` writes all of it, from values
+        that are zero where every rank's `flat` is zero: div_ in
+        _launch_bucket (0 / n), the all_reduce and broadcast collectives
+        and TSEngine's allreduce_sum (sums and copies of zeros), the
+        bf16 / fp16 wire round trips (_Bf16Work, the mpq and fp16
+        branches of _wan_tier: 0 -> 0 -> 0), wire_sum_2bit(out=flat) (a
+        zero gradient on a zero residual stays below the threshold and
+        decodes to 0) and wire_sum_bsc(out=flat) without DGT (zero
+        outside the lists; a listed padding element carries its zero
+        momentum). The optimizer kernels (ServerOptimizer.update) read
+        `flat` and write parameters and state only. The DGT wires are
+        the exception: their 4-bit tier decodes a chunk's values to
+        levels between the chunk's minimum and maximum, so an exact zero
+        need not come back as zero (wire_sum_dgt, wire_sum_bsc with
+        chunk_elems, DGTState.transform)."""
+        return self.cfg.compression not in ("dgt", "bsc_dgt")
 
     def _register_hooks(self):
         self._hook_handles = []
@@ -574,10 +613,14 @@ class GeoTrainer:
         is not cleared: its p.grad becomes None and its sink is re-armed,
         so the next backward writes the gradient into the span (or, off
         that route, the hook copies it there); until then p.grad is
-        None."""
+        None. Alignment padding between sink spans is not filled where
+        it cannot have changed (_pad_stays_zero); where it can, all gaps
+        of a bucket go in one launch."""
         for b in self.buckets:
             for r in b.clear:
                 r.zero_()
+            if b.gaps:
+                ops.zero_many_f32(b.gaps)
             b.ready = 0
         for p, sink in self.sinks.items():
             p.grad = None

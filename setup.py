@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "geomx_amd/csrc/conv.hip",
         "geomx_amd/csrc/convwrw2.hip",
         "geomx_amd/csrc/fc.hip",
+        "geomx_amd/csrc/finalize.hip",
         "geomx_amd/csrc/rowsparse.hip",
     ],
     extra_compile_args={
