@@ -73,7 +73,7 @@ class Config:
     hfa_k2: int = 1
 
     # --- compression --------------------------------------------------
-    # None | "2bit" | "bsc" | "fp16" | "mpq"
+    # None | "2bit" | "bsc" | "fp16" | "mpq" | "dgt" | "bsc_dgt" | "fp8"
     compression: Optional[str] = None
     # 2bit threshold (gradient_compression-inl.h:40-95)
     threshold: float = 0.5
@@ -82,6 +82,9 @@ class Config:
     # MPQ size gate: tensors with numel < size_lower_bound take the fp16
     # path, larger ones the bsc path (kvstore_dist_server.h:841,879)
     size_lower_bound: int = 200_000
+    # fp8 wire: elements per block-scaled E4M3 chunk, a power of two in
+    # [64, 8192] (one scale byte per chunk; GEOMX_FP8_BLOCK)
+    fp8_block: int = 256
 
     # --- DGT (differential gradient transmission) ---------------------
     # 0=off, 1..3 map the reference's channel modes (van.cc:736-748) to
@@ -135,6 +138,25 @@ class Config:
     backend: Optional[str] = None  # override; default nccl on GPU, gloo on CPU
     device: Optional[str] = None
 
+    def __post_init__(self):
+        self._validate_fp8()
+
+    def _validate_fp8(self):
+        """The fp8 tier's own rules, checked at construction and again by
+        validate(): the block size, and no TSEngine relay (the relay sums
+        dense or fp16 snapshots hop by hop; a tier with an error-feedback
+        residual has no place on it)."""
+        if self.compression != "fp8":
+            return
+        b = self.fp8_block
+        if not isinstance(b, int) or b < 64 or b > 8192 or b & (b - 1):
+            raise ValueError("fp8_block must be a power of two in "
+                             f"[64, 8192], got {b!r}")
+        if self.enable_ts:
+            raise ValueError("compression 'fp8' carries an error-feedback "
+                             "residual and is not supported on the TSEngine "
+                             "relay (enable_ts); use None or 'fp16' there")
+
     @staticmethod
     def from_env(**overrides) -> "Config":
         cfg = Config(
@@ -149,6 +171,7 @@ class Config:
             size_lower_bound=_env_int(
                 ["MXNET_KVSTORE_SIZE_LOWER_BOUND", "GEOMX_SIZE_LOWER_BOUND"], 200_000
             ),
+            fp8_block=_env_int(["GEOMX_FP8_BLOCK"], 256),
             enable_dgt=_env_int(["ENABLE_DGT", "GEOMX_ENABLE_DGT"], 0),
             dgt_k=_env_float(["DMLC_K", "GEOMX_DGT_K"], 0.5),
             dgt_k_min=_env_float(["DMLC_K_MIN"], 0.2),
@@ -181,8 +204,9 @@ class Config:
     def validate(self):
         if self.mode not in ("dist_sync", "dist_async", "local"):
             raise ValueError(f"mode must be dist_sync|dist_async|local, got {self.mode}")
-        if self.compression not in (None, "2bit", "bsc", "fp16", "mpq", "dgt", "bsc_dgt"):
+        if self.compression not in (None, "2bit", "bsc", "fp16", "mpq", "dgt", "bsc_dgt", "fp8"):
             raise ValueError(f"unknown compression {self.compression!r}")
+        self._validate_fp8()
         if not (0 < self.bsc_ratio < 1):
             raise ValueError("bsc_ratio must be in (0,1)")
         if self.num_parties < 1:

@@ -89,6 +89,12 @@ void geops_wire_sum_bsc_dgt(const float* const*, const int* const*,
 // dgtencode.hip
 int geops_dgt_encode(const float*, float*, const float*, const int*, float*,
                      uint8_t*, float*, long long, int, int, int, hipStream_t);
+// wirefp8.hip
+long long geops_fp8_wire_bytes(long long, int);
+int geops_fp8_encode(const float*, float*, uint8_t*, long long, int,
+                     hipStream_t);
+int geops_wire_sum_fp8(const void* const*, int, float*, long long, int, bool,
+                       hipStream_t);
 // bscselect.hip
 int geops_bsc_boundary_cap();
 int geops_bsc_boundary_grid(long long, int);
@@ -651,6 +657,63 @@ void dgt_encode(torch::Tensor x, torch::Tensor residual, torch::Tensor contrib,
       (int)nchunks, (int)n_keep, cur_stream());
   TORCH_CHECK(rc == 0, "dgt_encode: no kernel for chunk ", chunk);
   launch_check("dgt_encode");
+}
+
+// ---------------------------------------------------------------------------
+// FP8 wire tier (wirefp8.hip): block-scaled E4M3 payload of one bucket with
+// the residual update, and the fused decode-and-sum of all parties.
+// ---------------------------------------------------------------------------
+
+// chunk in the kernels' table and 1 <= n < 2^31; returns the payload bytes
+long long check_fp8_shape(const char* what, long long n, int64_t chunk) {
+  TORCH_CHECK(chunk >= 64 && chunk <= 8192 && (chunk & (chunk - 1)) == 0,
+              what, " serves a power-of-two chunk in [64, 8192], got ", chunk);
+  TORCH_CHECK(n >= 1 && n <= INT32_MAX, what, " serves 1 <= n < 2^31, got ",
+              n);
+  return geops_fp8_wire_bytes(n, (int)chunk);
+}
+
+void fp8_encode(torch::Tensor x, c10::optional<torch::Tensor> residual,
+                torch::Tensor payload, int64_t chunk) {
+  check_f32(x, "x");
+  const long long n = x.numel();
+  const long long bytes = check_fp8_shape("fp8_encode", n, chunk);
+  float* res = nullptr;
+  if (residual) {
+    check_f32(*residual, "residual");
+    TORCH_CHECK(residual->device() == x.device(),
+                "residual must be on x's device");
+    TORCH_CHECK(residual->numel() == n, "residual must have as many "
+                "elements as x (", residual->numel(), " vs ", n, ")");
+    res = residual->data_ptr<float>();
+  }
+  const void* pl = check_payload(payload, x, torch::kUInt8, bytes, "payload",
+                                 0);
+  TORCH_CHECK(((uintptr_t)pl & 15) == 0, "payload must be 16-byte aligned");
+  const int rc = geops_fp8_encode(x.data_ptr<float>(), res, (uint8_t*)pl, n,
+                                  (int)chunk, cur_stream());
+  TORCH_CHECK(rc == 0, "fp8_encode: no kernel for chunk ", chunk);
+  launch_check("fp8_encode");
+}
+
+void wire_sum_fp8(std::vector<torch::Tensor> payloads, torch::Tensor out,
+                  int64_t chunk, bool accumulate) {
+  check_f32(out, "out");
+  TORCH_CHECK(!payloads.empty(), "wire_sum_fp8 needs at least one party");
+  const long long n = out.numel();
+  const long long bytes = check_fp8_shape("wire_sum_fp8", n, chunk);
+  std::vector<const void*> ptrs;
+  for (size_t p = 0; p < payloads.size(); ++p) {
+    ptrs.push_back(check_payload(payloads[p], out, torch::kUInt8, bytes,
+                                 "payloads", p));
+    TORCH_CHECK(((uintptr_t)ptrs.back() & 15) == 0, "payloads[", p,
+                "] must be 16-byte aligned");
+  }
+  const int rc = geops_wire_sum_fp8(ptrs.data(), (int)ptrs.size(),
+                                    out.data_ptr<float>(), n, (int)chunk,
+                                    accumulate, cur_stream());
+  TORCH_CHECK(rc == 0, "wire_sum_fp8: no kernel for chunk ", chunk);
+  launch_check("wire_sum_fp8");
 }
 
 void relu_maxpool2_fwd(torch::Tensor in, torch::Tensor out, torch::Tensor idx,
@@ -1786,6 +1849,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // output elements per tile of k_wire_sum_bsc
   m.attr("WIRE_BSC_TILE") = geops_wire_sum_bsc_tile();
   m.def("dgt_encode", &dgt_encode);
+  m.def("fp8_encode", &fp8_encode);
+  m.def("wire_sum_fp8", &wire_sum_fp8);
   m.def("conv5_nhwc", &conv5_nhwc);
   m.def("pad_ch3to4_nhwc", &pad_ch3to4_nhwc);
   m.def("conv5_pack_frags", &conv5_pack_frags, py::arg("weight"),

@@ -53,6 +53,7 @@ wire-free and order-independent (test_async_push_flush_order_ws2).
 from __future__ import annotations
 
 
+import dataclasses
 import pickle
 from typing import Dict, List, Optional
 
@@ -71,7 +72,7 @@ class _KeyState:
     __slots__ = ("shape", "numel", "dtype", "stored", "update_buf",
                  "bsc_u", "bsc_v", "residual_2bit", "milestone",
                  "push_count", "owner_party", "dgt_contrib", "dgt_residual",
-                 "sliced", "padded", "residual_2bit_wan")
+                 "sliced", "padded", "residual_2bit_wan", "residual_fp8_wan")
 
     def __init__(self, shape, numel, dtype):
         self.shape = shape
@@ -90,6 +91,7 @@ class _KeyState:
         self.sliced = False   # P3/MultiGPS big-tensor slicing across leaders
         self.padded = 0       # padded numel (multiple of P) when sliced
         self.residual_2bit_wan: Optional[torch.Tensor] = None  # leader WAN tier
+        self.residual_fp8_wan: Optional[torch.Tensor] = None   # leader WAN tier
 
 
 class _UpdaterAdapter:
@@ -297,8 +299,15 @@ class KVStoreDist(KVStoreBase):
         self.flush()  # pending pushes complete under the OLD scheme
         params = dict(compression_params)
         ctype = params.get("type")
-        if ctype not in ("2bit", "bsc", "fp16", "mpq", "dgt", "bsc_dgt"):
+        if ctype not in ("2bit", "bsc", "fp16", "mpq", "dgt", "bsc_dgt",
+                         "fp8"):
             raise ValueError(f"unknown compression type {ctype!r}")
+        if ctype == "fp8":
+            # the rules of Config (block size, no TSEngine relay) hold for
+            # a type set at run time too
+            params.setdefault("block", self.cfg.fp8_block)
+            dataclasses.replace(self.cfg, compression="fp8",
+                                fp8_block=params["block"])
         if ctype == "2bit":
             params.setdefault("threshold", self.cfg.threshold)
             # untested/meaningless compositions are rejected loudly:
@@ -574,7 +583,7 @@ class KVStoreDist(KVStoreBase):
         """Leader-tier exchange. Returns the list of per-party
         contributions on ranks that must apply the update (owner in
         sharded mode / all leaders in replicated), else None. The
-        compressed wire formats (Bi-Sparse lists, 2bit, fp16, DGT mode 3)
+        compressed wire formats (Bi-Sparse lists, 2bit, fp8, fp16, DGT mode 3)
         return their fused sum as a one-element list, except where
         dist_async applies every party's contribution as an update of its
         own."""
@@ -645,6 +654,23 @@ class KVStoreDist(KVStoreBase):
                 return [ops.dequantize_2bit(p_, st.numel, thr)
                         for p_ in plist]
             return [ops.wire_sum_2bit(plist, st.numel, thr)]
+
+        if ctype == "fp8":
+            # block-scaled E4M3 codes with a WAN-side error-feedback
+            # residual per key: one payload tensor, one all_gather, one
+            # fused decode-and-sum
+            block = int(self.compression.get("block", self.cfg.fp8_block))
+            if st.residual_fp8_wan is None:
+                st.residual_fp8_wan = torch.zeros(st.numel,
+                                                  device=self._device)
+            payload = ops.fp8_encode(party_sum, st.residual_fp8_wan, block)
+            plist = [torch.empty_like(payload) for _ in range(P)]
+            comm.all_gather(plist, payload, group=group)
+            self.wan.charge(cross_party_bytes("all_gather",
+                                              payload.numel(), P))
+            if per_party:
+                return [ops.fp8_decode(p_, st.numel, block) for p_ in plist]
+            return [ops.wire_sum_fp8(plist, st.numel, block)]
 
         if ctype == "fp16":
             if self._ts is not None:
@@ -816,7 +842,7 @@ class KVStoreDist(KVStoreBase):
             return
         ctype = self._effective_ctype(st)
         need_wire = self.global_mode == "sharded" and not (
-            ctype in ("bsc", "fp16", "dgt", "2bit", "bsc_dgt")
+            ctype in ("bsc", "fp16", "dgt", "2bit", "fp8", "bsc_dgt")
             or self.cfg.mode == "dist_async")
         if not need_wire:
             return  # all leaders already hold the result (replayed update)
@@ -1176,7 +1202,7 @@ class KVStoreDist(KVStoreBase):
             return
         ctype = self._effective_ctype(st)
         need_wire = self.global_mode == "sharded" and not (
-            ctype in ("bsc", "fp16", "dgt", "2bit", "bsc_dgt")
+            ctype in ("bsc", "fp16", "dgt", "2bit", "fp8", "bsc_dgt")
             or self.cfg.mode == "dist_async")
         if not need_wire:
             return

@@ -407,6 +407,69 @@ def wire_sum_dgt(payloads, numel: int, chunk_elems: int,
     return ref.wire_sum_dgt(payloads, numel, chunk_elems, out, accumulate)
 
 
+# ---------------------------------------------------------------------------
+# FP8 wire tier: block-scaled E4M3 codes with error feedback (the format is
+# set out in ops.reference). k_fp8_encode is the send side, k_wire_sum_fp8
+# the fused receive side under the fold contract above.
+# ---------------------------------------------------------------------------
+
+fp8_wire_bytes = ref.fp8_wire_bytes
+
+
+def _fp8_aligned(*operands) -> bool:
+    """Contiguous fp32 / uint8 operands on 16 B boundaries, as the fp8
+    kernels read and write them (None: an absent residual)."""
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0
+               and t.dtype in (torch.float32, torch.uint8)
+               for t in operands if t is not None)
+
+
+def fp8_encode(x: torch.Tensor, residual: Optional[torch.Tensor],
+               chunk: int = 256) -> torch.Tensor:
+    """FP8 wire payload (uint8, fp8_wire_bytes(n, chunk)) of x + residual.
+    `residual` is updated in place with the quantization error; None means
+    zeros and no write-back. On the GPU one kernel does it all; operands it
+    does not serve (not fp32, or a view off a 16 B boundary) and CPU tensors
+    take ref.fp8_encode, whose bits the kernel reproduces up to the sign of
+    a code that is zero. A chunk outside the table raises on either path."""
+    flat = x.reshape(-1)
+    n = flat.numel()
+    nbytes = fp8_wire_bytes(n, chunk)
+    if _on_gpu(flat, residual) and 1 <= n < 2 ** 31 \
+            and _fp8_aligned(flat, residual):
+        g = _require_native()
+        res = None if residual is None else _flat_inplace(residual, "residual")
+        payload = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
+        g.fp8_encode(flat, res, payload, chunk)
+        return payload
+    return ref.fp8_encode(x, residual, chunk)
+
+
+def wire_sum_fp8(payloads, n: int, chunk: int = 256,
+                 out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    """Sum of the FP8 wire payloads of all parties, in fp32. On the GPU one
+    kernel decodes and sums them; payloads that are views off a 16 B
+    boundary, and CPU tensors, take the op sequence of ref.wire_sum_fp8."""
+    if _on_gpu(out, *payloads) and _fp8_aligned(*payloads):
+        g = _require_native()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32,
+                              device=payloads[0].device)
+            accumulate = False
+        g.wire_sum_fp8(list(payloads), _flat_inplace(out, "out"), chunk,
+                       accumulate)
+        return out
+    return ref.wire_sum_fp8(payloads, n, chunk, out, accumulate)
+
+
+def fp8_decode(payload: torch.Tensor, n: int, chunk: int = 256
+               ) -> torch.Tensor:
+    """Dense fp32 tensor of one FP8 wire payload: the one-party case of
+    wire_sum_fp8 (a code that is -0 comes back as +0)."""
+    return wire_sum_fp8([payload], n, chunk)
+
+
 # output elements per tile of k_wire_sum_bsc (None without the extension)
 WIRE_BSC_TILE = getattr(_geops, "WIRE_BSC_TILE", None)
 

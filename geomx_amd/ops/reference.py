@@ -373,6 +373,80 @@ def wire_sum_bsc(payloads, n: int, out: Optional[torch.Tensor] = None,
 
 
 # ---------------------------------------------------------------------------
+# FP8 wire tier: block-scaled OCP E4M3 with error feedback (no counterpart in
+# the reference; the tier between its fp16 transmission and DGT's 4 bits).
+# Payload of n elements at chunk C, nchunks = ceil(n / C), one uint8 tensor:
+#   nchunks * C code bytes (whole rows, positions >= n code 0), nchunks scale
+#   bytes (e + 127), zeros up to a multiple of 16.
+# One chunk of c = x + r:  amax = max |c| = m * 2^E, 1 <= m < 2;
+#   e = E - 8 if m <= 1.75 else E - 7, clamped to [-127, 127] (amax == 0:
+#   e = -127), so amax * 2^-e <= 448, the largest E4M3 value;
+#   code = RNE(c * 2^-e);  d = float(code) * 2^e;  r <- c - d.
+# ---------------------------------------------------------------------------
+
+def _fp8_nchunks(n: int, chunk: int) -> int:
+    if chunk < 64 or chunk > 8192 or chunk & (chunk - 1):
+        raise ValueError("the fp8 wire needs a power-of-two chunk in "
+                         "[64, 8192], got %r" % (chunk,))
+    return (n + chunk - 1) // chunk
+
+
+def fp8_wire_bytes(n: int, chunk: int = 256) -> int:
+    nchunks = _fp8_nchunks(n, chunk)
+    return (nchunks * chunk + nchunks + 15) // 16 * 16
+
+
+def fp8_exponent(amax: torch.Tensor) -> torch.Tensor:
+    """The chunk exponent e (int32) of each amax >= 0."""
+    m, ex = torch.frexp(amax)          # amax = m * 2^ex, 0.5 <= m < 1
+    e = ex - 9 + (m > 0.875).to(ex.dtype)
+    e = torch.where(amax == 0, torch.full_like(e, -127), e)
+    return e.clamp(-127, 127).to(torch.int32)
+
+
+def fp8_encode(x: torch.Tensor, residual: Optional[torch.Tensor],
+               chunk: int = 256) -> torch.Tensor:
+    """Payload of x + residual; `residual` (or None: zeros, no write-back)
+    is updated in place with the quantization error."""
+    flat = x.reshape(-1).float()
+    n = flat.numel()
+    nchunks = _fp8_nchunks(n, chunk)
+    c = torch.zeros(nchunks * chunk, dtype=torch.float32, device=flat.device)
+    c[:n] = flat if residual is None else flat + residual.reshape(-1)
+    rows = c.view(nchunks, chunk)
+    e = fp8_exponent(rows.abs().amax(dim=1))
+    codes = torch.ldexp(rows, -e[:, None]).to(torch.float8_e4m3fn)
+    if residual is not None:
+        d = torch.ldexp(codes.float(), e[:, None])
+        residual.reshape(-1).copy_((rows - d).reshape(-1)[:n])
+    payload = torch.zeros(fp8_wire_bytes(n, chunk), dtype=torch.uint8,
+                          device=flat.device)
+    payload[:nchunks * chunk] = codes.view(torch.uint8).reshape(-1)
+    payload[nchunks * chunk:nchunks * chunk + nchunks] = \
+        (e + 127).to(torch.uint8)
+    return payload
+
+
+def fp8_decode(payload: torch.Tensor, n: int, chunk: int = 256
+               ) -> torch.Tensor:
+    nchunks = _fp8_nchunks(n, chunk)
+    codes = payload[:nchunks * chunk].view(torch.float8_e4m3fn)
+    e = payload[nchunks * chunk:nchunks * chunk + nchunks].to(torch.int32) \
+        - 127
+    d = torch.ldexp(codes.float().view(nchunks, chunk), e[:, None])
+    return d.reshape(-1)[:n]
+
+
+def wire_sum_fp8(payloads, n: int, chunk: int = 256,
+                 out: Optional[torch.Tensor] = None,
+                 accumulate: bool = False) -> torch.Tensor:
+    acc = _wire_acc(n, payloads[0].device, out, accumulate)
+    for p in payloads:
+        acc += fp8_decode(p, n, chunk)
+    return acc if out is None else out
+
+
+# ---------------------------------------------------------------------------
 # FP16 transmission helpers (fp32 master copy semantics)
 # ---------------------------------------------------------------------------
 

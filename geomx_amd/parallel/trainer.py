@@ -51,7 +51,7 @@ from ..topology import Topology
 
 class _Bucket:
     __slots__ = ("params", "flat", "param_flat", "views", "ready", "expected",
-                 "work", "index", "bsc_u", "bsc_v", "dgt", "res2bit",
+                 "work", "index", "bsc_u", "bsc_v", "dgt", "res2bit", "resfp8",
                  "wan_buf", "wan_work", "wan_ready", "clear", "gaps",
                  "seg_off")
 
@@ -77,6 +77,7 @@ class _Bucket:
         self.bsc_v: Optional[torch.Tensor] = None
         self.dgt = None
         self.res2bit: Optional[torch.Tensor] = None  # 2bit WAN residual
+        self.resfp8: Optional[torch.Tensor] = None   # fp8 WAN residual
         # pipelined (dist_async) WAN tier state
         self.wan_buf: Optional[torch.Tensor] = None
         self.wan_work = None
@@ -145,7 +146,7 @@ class GeoTrainer:
                 and topo.num_parties > 1
                 and cfg.compression not in (None, "fp16")):
             # the pipelined one-step-stale WAN tier ships a dense or
-            # fp16 snapshot; stateful compressors (bsc/dgt/2bit error
+            # fp16 snapshot; stateful compressors (bsc/dgt/2bit/fp8 error
             # feedback) would need per-step residual bookkeeping across
             # the stale boundary — reject instead of silently running
             # lockstep (which is what an unguarded fall-through did)
@@ -259,7 +260,9 @@ class GeoTrainer:
         bf16 / fp16 wire round trips (_Bf16Work, the mpq and fp16
         branches of _wan_tier: 0 -> 0 -> 0), wire_sum_2bit(out=flat) (a
         zero gradient on a zero residual stays below the threshold and
-        decodes to 0) and wire_sum_bsc(out=flat) without DGT (zero
+        decodes to 0), wire_sum_fp8(out=flat) (a zero element on a zero
+        residual has code 0 at any chunk scale, decodes to 0 and leaves
+        its residual zero) and wire_sum_bsc(out=flat) without DGT (zero
         outside the lists; a listed padding element carries its zero
         momentum). The optimizer kernels (ServerOptimizer.update) read
         `flat` and write parameters and state only. The DGT wires are
@@ -579,6 +582,20 @@ class GeoTrainer:
                     self.wan.charge(cross_party_bytes(
                         "all_gather", packed.numel() * 4, P))
                     ops.wire_sum_2bit(plist, b.flat.numel(), thr, out=b.flat)
+                elif ctype == "fp8":
+                    # block-scaled E4M3 codes with WAN-side error
+                    # feedback: one payload per bucket, one fused
+                    # decode-and-sum of all parties. b.flat is no input of
+                    # the sum: the payload was made from it above
+                    if b.resfp8 is None:
+                        b.resfp8 = torch.zeros_like(b.flat)
+                    block = self.cfg.fp8_block
+                    payload = ops.fp8_encode(b.flat, b.resfp8, block)
+                    plist = [torch.empty_like(payload) for _ in range(P)]
+                    comm.all_gather(plist, payload, group=topo.leader_group)
+                    self.wan.charge(cross_party_bytes(
+                        "all_gather", payload.numel(), P))
+                    ops.wire_sum_fp8(plist, b.flat.numel(), block, out=b.flat)
                 elif ctype in ("fp16", "mpq"):
                     if self._ts is not None:
                         # TSEngine relay (charges per hop internally)

@@ -134,6 +134,43 @@ def dgt_encode_rows(n, iters, report, results):
         torch.cuda.empty_cache()
 
 
+def fp8_wire_rows(n, iters, report, results, chunk=256, P=4):
+    """FP8 wire tier. k_fp8_encode against its byte model (x and the
+    residual in, the residual and one code byte per element out: 13 B per
+    element, plus a scale byte per chunk), and k_wire_sum_fp8 at P parties
+    beside k_wire_sum_f16 at the same n and P, in alternating windows. The
+    spread is (max - min) / median over the 7 windows."""
+    dev = "cuda:0"
+    iters = max(5, iters // 5)
+    grads = [torch.randn(n, device=dev) for _ in range(P)]
+    res = 0.01 * torch.randn(n, device=dev)
+    nbytes = ops.fp8_wire_bytes(n, chunk)
+    dst = torch.empty(n, device=dev)
+    pl = [ops.fp8_encode(g, None, chunk) for g in grads]
+    hl = [g.half() for g in grads]
+    del grads[1:]
+
+    def encode():
+        ops.fp8_encode(grads[0], res, chunk)
+    te = sum(window_pair(encode, encode, iters), [])   # 14 windows of it
+    me = sorted(te)[len(te) // 2]
+    report("fp8_encode(c=%d)" % chunk, 12 * n + nbytes, me)
+    results[-1].update(spread=round((max(te) - min(te)) / me, 3))
+    print("%24s spread between windows %.1f%%"
+          % ("", 100 * results[-1]["spread"]))
+    t8, t16 = window_pair(
+        lambda: ops.wire_sum_fp8(pl, n, chunk, out=dst),
+        lambda: ops.wire_sum_fp16(hl, out=dst), iters)
+    m8, m16 = sorted(t8)[len(t8) // 2], sorted(t16)[len(t16) // 2]
+    report("wire_sum_fp8 P=%d" % P, P * nbytes + 4 * n, m8)
+    results[-1].update(spread=round((max(t8) - min(t8)) / m8, 3))
+    report("wire_sum_fp16 P=%d" % P, P * 2 * n + 4 * n, m16)
+    results[-1].update(spread=round((max(t16) - min(t16)) / m16, 3))
+    print("%24s fp8 / fp16 time %.3f; spread between windows %.1f%% fp8, "
+          "%.1f%% fp16" % ("", m8 / m16, 100 * results[-2]["spread"],
+                           100 * results[-1]["spread"]))
+
+
 def wire_reduce_rows(n, iters, report, results):
     """Fused wire reduce against the chain of single-party ops it replaced
     at the receive sites, P = 2 and 8. Bytes are those that must move:
@@ -347,6 +384,8 @@ def main():
                     help="only the Bi-Sparse boundary rows, chain and kernel")
     ap.add_argument("--only-dgt", action="store_true",
                     help="only the fused DGT encode rows")
+    ap.add_argument("--only-fp8", action="store_true",
+                    help="only the FP8 wire rows, beside the fp16 sum")
     ap.add_argument("--only-lars", action="store_true",
                     help="only the LBSGD 'lars' rows")
     args = ap.parse_args()
@@ -387,6 +426,11 @@ def main():
     if args.only_dgt:
         del g
         dgt_encode_rows(n, args.iters, report, results)
+        dump()
+        return
+    if args.only_fp8:
+        del g
+        fp8_wire_rows(n, args.iters, report, results)
         dump()
         return
     if args.only_lars:
@@ -504,6 +548,7 @@ def main():
     wire_reduce_rows(n, args.iters, report, results)
     wire_sparse_rows(n, args.iters, report, results)
     dgt_encode_rows(n, args.iters, report, results)
+    fp8_wire_rows(n, args.iters, report, results)
     lars_rows(n, args.iters, report, results)
     dump()
 

@@ -49,6 +49,8 @@ ext = CUDAExtension(
 # instantiation conv.hip keeps building as before; conv1u8.hip is the uint8
 # instantiation of the same template, built like its fp32 sibling. lars.hip (layer-wise LARS)
 # specifies its sums of squares one rounded operation at a time and is too.
+# wirefp8.hip (the FP8 wire tier) adds the residual, subtracts the decoded
+# value and folds the parties one rounded operation at a time and is too.
 # The extension's flag list is one for all of its sources, so these are
 # compiled here, with the same flags plus the feature switch, and linked
 # into _geops as objects. They include no torch header.
@@ -59,7 +61,8 @@ NO_PK_F32_SOURCES = ["geomx_amd/csrc/wirereduce.hip",
                      "geomx_amd/csrc/bscselect.hip",
                      "geomx_amd/csrc/conv1x32.hip",
                      "geomx_amd/csrc/conv1u8.hip",
-                     "geomx_amd/csrc/lars.hip"]
+                     "geomx_amd/csrc/lars.hip",
+                     "geomx_amd/csrc/wirefp8.hip"]
 NO_PK_F32_DEPENDS = ["geomx_amd/csrc/wire_codec.h",
                      "geomx_amd/csrc/bsc_mom.h",
                      "geomx_amd/csrc/conv5_common.h",
